@@ -6,11 +6,17 @@ whole matrix, inputs resident in HBM (what the reference times around assemble_s
 examples/poisson.cc:1099-1103).  Workload = BASELINE.json configs[2]: unit cube, 64^3 hex background
 mesh, 32^3 = 32 768 polytopes of 2x2x2 cells, p = 3, QGauss(4) cell and face rules (examples/poisson.cc:
 702-709), SIP variant of examples/poisson.cc.  Headline FE is FE_DGQ(3) ((p+1)^3 = 64 dofs/polytope,
-2 097 152 dofs); the FE_AggloDGP(3) number (20 dofs/polytope, what poisson.cc instantiates) is reported
+2 097 152 dofs); with --full the FE_AggloDGP(3) number (20 dofs/polytope, what poisson.cc instantiates) is reported
 under "extra".  N > 1 (one rank per GPU): STRONG scaling by default (BASELINE.json north_star: ">= 6x strong scaling to
 8 GPUs") - the N = 1 problem split into N contiguous row ranges of whole polytopes, every rank describing only its own
 polytopes and their ghost neighbours; `--scaling weak` stacks N such cubes along z instead (subdivided_hyper_rectangle,
 64 x 64 x 64N cells, ONE connected problem, rank r owns slab r).  Either way every rank owns its rows outright (owner-computes-rows): the data path has no collective.
+
+A plain run sets up the headline problem, warms up, times --steps steps and prints the line: `value`, `ms_per_step`, the
+roofline of those steps (HIP events of the same launches) and the on-device checksum of the matrix they left.  --full adds
+every secondary measurement (other element, lower degrees, irregular and distorted meshes, end-to-end, direct form,
+right-hand-side / evaluation kernels, CPU baseline; N > 1: ghost-block exchange).  --dump-outputs DIR writes the CSR values
+of the last timed step (float64; a fixed seeded sample beyond DUMP_MAX_VALUES) for output-for-output comparison of builds.
 
 Prints ONE JSON line on rank 0.
 """
@@ -25,6 +31,20 @@ sys.path.insert(0, ROOT)
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 matrix (= vector) peak, datasheet; see DESIGN.md
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_MAX_VALUES = 1 << 22  # --dump-outputs: at most 32 MB of float64 values over all ranks
+
+
+def dump_outputs(ctx, out_dir, rank, world):
+    """--dump-outputs: the CSR values the timed steps left in HBM - what pdh_assemble_device hands its caller - as float64.
+    Matrices of up to DUMP_MAX_VALUES values (per rank: / world) whole; larger ones as the values at a fixed sample of
+    positions (seed 0, ascending), the same for the same arguments."""
+    import numpy as np
+    vals = ctx.values()
+    cap = DUMP_MAX_VALUES // world
+    if vals.size > cap:
+        vals = vals[np.sort(np.random.default_rng(0).choice(vals.size, cap, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "csr_values.npy" if world == 1 else "csr_values_rank%d.npy" % rank), vals)
 
 
 def algorithmic_work(flat, n, owned=None):
@@ -108,7 +128,7 @@ def build_handler(pa, dim, cells, block, basis, degree, nq, stack=1, grown=False
 
 
 def run_gpu(pa, torch, dist, args, basis, rank, world, local_rank, steps, warmup, alg="auto", look_for_tensor_rules=True, grown=False,
-            distort=0.0, diag_first=True):
+            distort=0.0, diag_first=True, dump_dir=None):
     t0 = time.time()
     stack = world if args.scaling == "weak" else 1
     grid, ah, fe = build_handler(pa, args.dim, args.cells, args.block, basis, args.degree, args.degree + 1, stack, grown, distort)
@@ -167,6 +187,8 @@ def run_gpu(pa, torch, dist, args, basis, rank, world, local_rank, steps, warmup
     dt = time.perf_counter() - t1
     kms, nl = ctx.kernel_times_ms()
     ctx.set_profiling(False)
+    if dump_dir:
+        dump_outputs(ctx, dump_dir, rank, world)
     dt_overlap = None
     if args.overlap_extra:
         ctx.set_overlap(True)
@@ -225,17 +247,18 @@ def run_gpu(pa, torch, dist, args, basis, rank, world, local_rank, steps, warmup
             exp += float(np.sum(arr["face_sigma"][bd] * fw[bd]))
         validity.update(expected_sum=exp, rel_err=abs(cs["sum"] - exp) / max(abs(exp), 1e-300),
                         note="sum of all entries = 1^T A 1 = sum_bdry sigma |F| + c |Omega| for FE_DGQ")
-    vals = ctx.assemble() if stats["n_values"] <= 64_000_000 else None
+    ghost_extra = world > 1 and args.full and args.exchange_extra and alg == "auto"
+    vals = ctx.assemble() if ghost_extra and stats["n_values"] <= 64_000_000 else None
     chk = validity
     aux = None
-    if world == 1 and args.aux_kernels and alg == "auto" and look_for_tensor_rules and not grown:
+    if world == 1 and args.full and args.aux_kernels and alg == "auto" and look_for_tensor_rules and not grown:
         try:
             aux = time_aux_kernels(torch, ctx, flat, n, stats)
         except Exception as exc:
             aux = {"error": repr(exc)}
     ctx.close()
     ghost = None
-    if world > 1 and args.exchange_extra and alg == "auto":
+    if ghost_extra:
         try:
             ghost = run_ghost_exchange(pa, torch, dist, args, flat, r0, r1, rank, world, local_rank, steps, warmup, vals)
         except Exception as exc:  # the measured default path above must not be lost to a failure of the extra variant
@@ -528,6 +551,12 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="N > 1: strong (default; BASELINE.json north_star asks for strong scaling to 8 GPUs) = the N = 1 problem "
                          "split into N contiguous row ranges; weak = N cubes stacked along the last direction, one slab per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (extra.*, roofline.direct_form, cpu_baseline; N > 1: "
+                         "config.exchange_variant); the --no-* options below leave parts of it out.  Off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the CSR values of the last timed step to DIR/csr_values.npy (float64; matrices above %d "
+                         "values as a fixed seeded sample of that many)" % DUMP_MAX_VALUES)
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary FE measurement")
     ap.add_argument("--general-points-extra", action="store_true",
                     help="also time the row kernel's general-point paths (quadrature declared unstructured); off by default: "
@@ -586,10 +615,12 @@ def main():
 
     import polydeal_amd as pa
 
-    main_res = run_gpu(pa, torch, dist, args, args.fe, rank, world, local_rank, args.steps, args.warmup)
+    main_res = run_gpu(pa, torch, dist, args, args.fe, rank, world, local_rank, args.steps, args.warmup,
+                       dump_dir=args.dump_outputs)
     extra = {}
     other = "dgp" if args.fe == "dgq" else "dgq"
-    if not args.no_extra:
+    extras = args.full and not args.no_extra
+    if extras:
         r2 = run_gpu(pa, torch, dist, args, other, rank, world, local_rank, args.steps, args.warmup)
         extra = {"fe": ("FE_AggloDGP" if other == "dgp" else "FE_DGQ") + "(%d)" % args.degree,
                  "dofs_per_polytope": r2["n"], "n_dofs": r2["n_dofs"],
@@ -605,7 +636,7 @@ def main():
                                     "charges (more than half of it for FE_AggloDGP(3)): measured traffic in "
                                     "profiles/r04b_hbm_small_elements.txt") if r2["rows_kernel"] == "terms" else None,
                          fp64_bound_ms=1e3 * sum(r2["work"]["flops"]) / (FP64_PEAK_TFLOPS * 1e12))
-    if not args.no_extra and world == 1 and main_res.get("rows_kernel") == "terms" and main_res["n"] == 64:
+    if extras and world == 1 and main_res.get("rows_kernel") == "terms" and main_res["n"] == 64:
         # the same workload through the kernel that was AUTO's choice for FE_DGQ(3) until round 4 (pdh_rows.h: moment form + MFMA
         # contraction, one wave per polytope), same process, same device
         os.environ["PDH_TERMS_DGQ3"] = "0"
@@ -618,7 +649,7 @@ def main():
             extra["pdh_rows_h"] = {"error": str(e)[:200]}
         finally:
             del os.environ["PDH_TERMS_DGQ3"]
-    if not args.no_extra and world == 1 and args.dim == 3 and args.degree == 3:
+    if extras and world == 1 and args.dim == 3 and args.degree == 3:
         # the lower degrees of the same mesh (streamed kinds of the row kernel; degree 2 is the element of BASELINE configs[1] / [3])
         import copy
         extra["lower_degrees"] = []
@@ -636,7 +667,7 @@ def main():
                 extra["lower_degrees"].append({"degree": p_low, "error": repr(exc)})
     if main_res.get("aux") is not None:
         extra["aux_kernels"] = main_res["aux"]
-    if not args.no_extra and world == 1 and args.dim == 3:
+    if extras and world == 1 and args.dim == 3:
         # the same cells agglomerated the way the reference's own callers do it (examples/poisson.cc:543-566: METIS on the cell
         # graph; here regions grown over the graph - METIS is not available offline): irregular connected polytopes of about
         # block^3 cells, neighbours met along several planes ("staircase" faces), 2-3x as many neighbours as a block has
@@ -668,7 +699,7 @@ def main():
             extra["irregular_agglomerates"]["other_element"] = line6
         except Exception as exc:
             extra["irregular_agglomerates"] = {"error": repr(exc)}
-    if not args.no_extra and world == 1 and args.dim == 3:
+    if extras and world == 1 and args.dim == 3:
         # Non-Cartesian cells (the reference's own defaults: examples/3D_piston.cc:396-400, exact_solutions_dgp.cc:306): the headline
         # mesh with every interior vertex moved by up to 0.1 h - faces are no longer planar, quadrature rules no longer tensor
         # rules, so AUTO leaves the row kernels; what it takes instead and what that costs by the same SURVEY 8(d) byte count
@@ -688,7 +719,7 @@ def main():
                                                       "frac_of_hbm_peak": by8 / t8a * 1e-9 / HBM_PEAK_GBS}
         except Exception as exc:
             extra["distorted"] = {"error": repr(exc)}
-    if world == 1 and not args.no_extra and args.dim == 3:
+    if world == 1 and extras and args.dim == 3:
         try:
             extra["end_to_end"] = end_to_end(pa, args)
         except Exception as exc:
@@ -699,7 +730,7 @@ def main():
         except Exception as exc:
             extra["strong_proxy"] = {"error": repr(exc)}
     direct = None
-    if main_res["alg"] != "direct" and not args.no_extra:
+    if main_res["alg"] != "direct" and extras:
         # the same workload through the direct (MFMA contraction) form, for the record
         direct = run_gpu(pa, torch, dist, args, args.fe, rank, world, local_rank, max(3, args.steps // 3), 1, alg="direct")
 
@@ -709,7 +740,7 @@ def main():
         general = run_gpu(pa, torch, dist, args, args.fe, rank, world, local_rank, max(3, args.steps // 3), 1,
                           look_for_tensor_rules=False)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
       try:  # a failure of the CPU leg must not discard the GPU measurement already taken
         res, cores = cpu_baseline(pa, args, args.fe)
         a, o = res["port"]["all"], res["port"]["one"]

@@ -320,6 +320,52 @@ def test_bench_strong_scaling_rehearsal_on_one_gpu():
     assert d["value"] > 0 and d["roofline"]["kernel"] == "k_terms_wg"  # (rank-local descriptions: the workgroup term kernel)
 
 
+def run_bench(*args):
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + [str(a) for a in args], capture_output=True,
+                         text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times --steps launches of the headline problem and nothing else; --dump-outputs writes the
+    CSR values of the last timed step: whole for a small matrix (their sum is the on-device checksum), a fixed sample of
+    bench.DUMP_MAX_VALUES for a larger one, at the same positions with the same values in a second run."""
+    import bench
+
+    d = run_bench("--cells", 8, "--steps", 3, "--warmup", 1, "--dump-outputs", tmp_path / "a")
+    assert d["steps"] == 3 and d["roofline"]["launches_timed"] == 3 and d["ms_per_step"] > 0
+    assert d["extra"] == {} and d["cpu_baseline"] is None and "direct_form" not in d["roofline"]
+    a = np.load(tmp_path / "a" / "csr_values.npy")
+    n_agg, n = 4 ** 3, 64
+    assert a.dtype == np.float64 and a.size == n * n * (n_agg + 2 * 3 * 4 * 4 * 3)
+    assert d["checksum"]["non_finite"] == 0 and abs(a.sum() - d["checksum"]["sum"]) <= 1e-12 * np.abs(a).sum()
+
+    dumps = []
+    for name in ("b", "c"):
+        run_bench("--cells", 16, "--steps", 2, "--warmup", 1, "--dump-outputs", tmp_path / name)
+        dumps.append(np.load(tmp_path / name / "csr_values.npy"))
+    assert dumps[0].size == bench.DUMP_MAX_VALUES and np.all(np.isfinite(dumps[0]))
+    assert np.max(np.abs(dumps[0] - dumps[1])) <= 1e-12 * np.max(np.abs(dumps[0]))
+
+
+def test_bench_full_run_keeps_the_secondary_measurements():
+    """`bench.py --full` (here without the CPU baseline, which sizes itself to seconds of host time) still runs every
+    secondary measurement of the bench and records no error in any of them."""
+    import json
+
+    d = run_bench("--full", "--no-cpu-baseline", "--cells", 16, "--steps", 2, "--warmup", 1)
+    for key in ("fe", "lower_degrees", "aux_kernels", "irregular_agglomerates", "distorted", "end_to_end"):
+        assert key in d["extra"], key
+    assert '"error"' not in json.dumps(d["extra"]), d["extra"]
+
+
 def test_config3_distorted_mesh_fullsize():
     """The headline mesh with every interior vertex moved by up to 0.1 h (general hexahedra, non-planar faces: what the reference's
     own defaults look like - examples/3D_piston.cc:396-400, test/polydeal/exact_solutions_dgp.cc:306): AUTO leaves the row kernels

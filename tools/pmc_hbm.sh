@@ -5,8 +5,8 @@ TAG=${1:-hbm}; shift
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/f -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra "$@" > $OUT/f.json 2> $OUT/f.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/w -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra "$@" > $OUT/w.json 2> $OUT/w.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/f -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra "$@" > $OUT/f.json 2> $OUT/f.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/w -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra "$@" > $OUT/w.json 2> $OUT/w.err
 python3 - <<PY
 import csv, collections, json
 agg=collections.defaultdict(list)

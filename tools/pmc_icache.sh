@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 rocprofv3 -L > $OUT/counters.txt 2>&1
 grep -o "SQC_ICACHE[A-Z_]*\|SQ_IFETCH[A-Z_]*\|SQ_WAIT_IFETCH[A-Z_]*\|SQC_TC_[A-Z_]*\|SQ_BUSY_CU_CYCLES\|SQ_WAVES\b" $OUT/counters.txt | sort -u | tr '\n' ' '
 echo
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVES --kernel-trace --output-format csv -d $OUT/a -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/a.json 2> $OUT/a.err
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVES --kernel-trace --output-format csv -d $OUT/a -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/a.json 2> $OUT/a.err
 python3 - <<PY
 import csv, collections
 try:
