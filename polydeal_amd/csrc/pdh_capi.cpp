@@ -1886,8 +1886,15 @@ static bool build_terms_tables(const pdh_problem *p, const Packed &K, const Rows
   const int basis = p->basis == PDH_BASIS_AGGLODGP ? 1 : 0;
   if (p->dim != 3 || !pdh_terms_has_kind(K.n1d, basis))
     return no("term kernel: 3-D FE_DGQ(1,2) / FE_AggloDGP(1..3) only");
-  if (!RH.planar_ok || RH.fq_tensor_n <= 0 || vq_n <= 0 || (int)K.own_agg.size() != K.n_owned)
-    return no("term kernel: needs axis-aligned planar faces and tensor-product rules on every sub-cell and sub-face");
+  // (which condition failed: origins far from zero leave the rules tensor-product only to more than geometry_rounding allows)
+  if (!RH.planar_ok)
+    return no("term kernel: needs faces that are unions of axis-aligned planes");
+  if (RH.fq_tensor_n <= 0)
+    return no("term kernel: needs tensor-product rules on every sub-face (the face points are not, to the rounding bound of the geometry)");
+  if (vq_n <= 0)
+    return no("term kernel: needs tensor-product rules on every sub-cell (the volume points are not, to the rounding bound of the geometry)");
+  if ((int)K.own_agg.size() != K.n_owned)
+    return no("term kernel: exchange variant");
   const int fn = RH.fq_tensor_n;
   const int64_t gsz = (int64_t)fn * fn, m3 = (int64_t)vq_n * vq_n * vq_n;
   const size_t nruns = K.run_ap.size();
@@ -2120,7 +2127,7 @@ extern "C" int pdh_check_terms(const pdh_problem *p, int32_t row_begin, int32_t 
   (void)build_rows_tables(p, K, R, &why);
   if (!R.planar_ok)
     {
-      g_err_noctx = why;
+      g_err_noctx = why.empty() ? std::string("term kernel: faces are not unions of axis-aligned planes") : why;
       return 0;
     }
   const int vn = resolve_tensor_hint(p->vq_tensor_n, [&](int n) { return volume_rules_are_tensor(p, K, n); });
@@ -2132,7 +2139,7 @@ extern "C" int pdh_check_terms(const pdh_problem *p, int32_t row_begin, int32_t 
       stats5[0] = TH.maxruns, stats5[1] = TH.maxsf, stats5[2] = TH.maxsi, stats5[3] = TH.maxcell, stats5[4] = TH.lds_bytes;
     }
   if (!ok)
-    g_err_noctx = why_t;
+    g_err_noctx = why_t.empty() ? std::string("term kernel: refused (no reason recorded)") : why_t;
   return ok ? 1 : 0;
 }
 

@@ -6,6 +6,8 @@ unit cube [0,1]^d and uniform penalty sigma
 These touch every kernel output (diagonal blocks, both coupling blocks of every face, CSR placement incl. the
 deal.II diagonal-first layout).  The same identities are what test/polydeal/poisson_sanity_check_01..03 print
 (there with boundary terms dropped)."""
+import math
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -72,8 +74,8 @@ def run_identities(dim, cells, block, fe, nq, unstructured_rules=None, distort=0
         # (per-face sums by reduceat: differences of a running sum over 14 M weights would carry 1e-11 of rounding themselves)
         area = np.add.reduceat(w, fp[:-1])
         x2 = np.add.reduceat(w * x0q * x0q, fp[:-1])
-        bdry_sigma_area = float(np.sum(arr["face_sigma"][bd] * area[bd]))
-        bdry_sigma_x2 = float(np.sum(arr["face_sigma"][bd] * x2[bd]))
+        bdry_sigma_area = math.fsum(arr["face_sigma"][bd] * area[bd])
+        bdry_sigma_x2 = math.fsum(arr["face_sigma"][bd] * x2[bd])
         ctx = pa.Context(0)
         ctx.set_problem(flat)
         if expect_alg is not None:
@@ -115,11 +117,11 @@ def run_identities(dim, cells, block, fe, nq, unstructured_rules=None, distort=0
     q1 = float(v1 @ y1)
     qx = float(vx @ (A @ vx))
     if distort:  # v = 1: sum over the boundary faces of sigma_F |F|; v = x_0: 1 - 2 + sum_F sigma_F int_F x_0^2
-        # (bound: entries good to 1e-12 relative, coefficients |v| <= 1 - the quadratic forms are sums of 9e8 entries that cancel
-        # to 1e-2 of their absolute sum, so the result itself carries fewer digits than an entry)
-        tol = 1e-12 * float(np.sum(np.abs(vals)))
-        assert abs(q1 - bdry_sigma_area) <= tol, (q1, bdry_sigma_area, tol)
-        assert abs(qx - (-1.0 + bdry_sigma_x2)) <= tol, (qx, -1.0 + bdry_sigma_x2, tol)
+        # (reference values: exact sums (math.fsum) of the per-face sums, 1e-11 relative to them - the quadratic forms are sums of
+        # 9e8 entries that cancel to 1e-2 of their absolute sum)
+        ex1, exx = bdry_sigma_area, -1.0 + bdry_sigma_x2
+        assert abs(q1 - ex1) <= 1e-11 * abs(ex1), (q1, ex1, (q1 - ex1) / ex1)
+        assert abs(qx - exx) <= 1e-11 * abs(exx), (qx, exx, (qx - exx) / exx)
         sample = np.unique(np.linspace(0, ah.n_dofs - 1, 400).astype(np.int64))
         S = A[sample][:, sample]
         assert abs(S - S.T).max() <= 1e-12 * scale
@@ -374,3 +376,67 @@ def test_config3_distorted_mesh_fullsize():
     assert n_dofs == 2097152 and nnz == 914358272
     n_dofs, nnz = run_identities(3, 64, 2, pa.FE_AggloDGP(3, 3), 4, distort=0.1, expect_alg="direct")
     assert n_dofs == 655360 and nnz == 89292800
+
+
+def test_config3_anisotropic_box_fullsize():
+    """The headline element and size on a box of cells that are not cubes: 64^3 cells on [0,2] x [0,1] x [0,0.5] (h = 1/32, 1/64,
+    1/128), 2^3 blocks, FE_DGQ(3) - AUTO's k_terms_wg, the kernel behind the bench figure.  A 1 = 0 on interior rows, and with the
+    uniform sigma of equal blocks
+        1^T A 1     = sigma |dOmega|
+        x_c^T A x_c = -|Omega| + sigma int_dOmega x_c^2     for c = 0, 1, 2 (a swapped axis factor changes these)
+    each to 1e-11 relative; symmetry on a sample of rows."""
+    lo, hi = np.zeros(3), np.array([2.0, 1.0, 0.5])
+    fe = pa.FE_DGQ(3, 3)
+    grid = pa.BackgroundGrid.subdivided_hyper_rectangle(3, (64, 64, 64), lo, hi)
+    ah = pa.AgglomerationHandler(grid)
+    ah.define_block_agglomerates(2)
+    ah.initialize_fe_values(4, 4)
+    ah.distribute_agglomerated_dofs(fe)
+    assert ah.n_dofs == 2097152
+    var = pa.SipVariant.poisson_example(fe)
+    flat = ah.flatten(var, True, True)
+    ctx = pa.Context(0)
+    ctx.set_problem(flat)
+    assert ctx.algorithm_in_use() == "rows" and ctx.rows_kernel_in_use() == "terms"
+    vals = ctx.assemble()
+    ctx.close()
+    arr = flat.arrays()
+    rp, ci = arr["rowptr"].copy(), arr["colind"].copy()
+    del flat, arr
+    assert np.all(np.isfinite(vals)) and len(vals) == 914358272
+    A = sp.csr_matrix((vals, ci, rp), shape=(ah.n_dofs, ah.n_dofs))
+    del ci
+    scale = float(np.max(np.abs(vals)))
+    n, nA, p = fe.n_dofs_per_cell, ah.n_agglomerates, fe.degree
+    sigma = var.penalty_constant / ah.diameter(0)
+    assert all(ah.diameter(P) == ah.diameter(0) for P in range(0, nA, 997))
+    from oracle.polydeal_oracle import gauss_lobatto_nodes  # node positions only (test infrastructure)
+    nodes = gauss_lobatto_nodes(p)
+    blo, bhi = np.zeros((nA, 3)), np.zeros((nA, 3))
+    off = np.zeros(nA, dtype=np.int64)
+    for P in range(nA):
+        blo[P], bhi[P] = ah.bbox(P)
+        off[P] = ah.dof_indices(P)[0]
+    idx = off[:, None] + np.arange(n)[None, :]
+    v1 = np.ones(ah.n_dofs)
+    y1 = A @ v1
+    interior = np.all(blo > 1e-12, axis=1) & np.all(bhi < hi - 1e-12, axis=1)
+    assert interior.sum() == 30 ** 3
+    assert np.max(np.abs(y1[idx[interior].ravel()])) <= 1e-12 * scale * n
+    L = hi - lo
+    faces = np.array([L[1] * L[2], L[0] * L[2], L[0] * L[1]])
+    e1 = sigma * 2.0 * faces.sum()
+    q1 = float(v1 @ y1)
+    assert abs(q1 - e1) <= 1e-11 * e1, (q1, e1)
+    for c in range(3):
+        digit = (np.arange(n) // (p + 1) ** c) % (p + 1)  # lexicographic, x fastest
+        vx = np.zeros(ah.n_dofs)
+        vx[idx] = blo[:, c:c + 1] + nodes[digit][None, :] * (bhi - blo)[:, c:c + 1]
+        # int_dOmega x_c^2: the faces x_c = lo_c, hi_c, and the other four with the mean of x_c^2 over [lo_c, hi_c]
+        x2 = faces[c] * (lo[c] ** 2 + hi[c] ** 2) + 2.0 * (faces.sum() - faces[c]) * (hi[c] ** 3 - lo[c] ** 3) / (3.0 * L[c])
+        ex = -float(np.prod(L)) + sigma * x2
+        qx = float(vx @ (A @ vx))
+        assert abs(qx - ex) <= 1e-11 * abs(ex), (c, qx, ex)
+    sample = np.unique(np.linspace(0, ah.n_dofs - 1, 400).astype(np.int64))
+    S = A[sample][:, sample]
+    assert abs(S - S.T).max() <= 1e-12 * scale
