@@ -134,6 +134,15 @@ static int combo_group(int dim, int n1d, int nt, int lb)
   return -1;
 }
 
+// which row kernel serves a problem (plan_kernels): none, the kinds of pdh_rows.h, or the term kernels (pdh_terms.h /
+// pdh_terms_wg.h)
+enum class RowKernel
+{
+  none,
+  rows,
+  terms
+};
+
 struct pdh_ctx
 {
   int device = 0;
@@ -192,18 +201,17 @@ struct pdh_ctx
   // moment form (pdh_moment.h): available for 3-D bases of degree <= 3; `algorithm` = caller's choice
   int algorithm = PDH_ALG_AUTO;
   int basis = 0;
-  double *d_mtab = nullptr;
-  // row kernel (pdh_rows.h): available when every face of every owned polytope is an axis-aligned plane (FE_DGQ(3), 3-D)
-  bool rows_ok = false;
-  bool rows_auto = true; // AUTO takes the row kernel where it applies (degree 1 since 12 waves per CU are resident: 0.21 vs 0.24-0.30 ms)
+  const double *d_mtab = nullptr;
+  // The row kernel of the problem, if any (set_problem builds the device state of that one only): pdh_rows.h where every face
+  // of every owned polytope is a union of axis-aligned planes; the term kernel (pdh_terms.h) on agglomerates of Cartesian cells
+  // with tensor rules - any number of planes per neighbour - is taken instead wherever its tables fit the LDS budget.
+  RowKernel row_kernel = RowKernel::none;
   PdhRows rows;
-  // term kernel (pdh_terms.h): the row kernel of the small elements on agglomerates of Cartesian cells with tensor rules - any
-  // number of planes per neighbour; taken instead of the streamed kinds of pdh_rows.h wherever its tables fit the LDS budget
-  bool terms_ok = false;
   PdhTerms terms;
+  // AUTO takes the row kernel where it applies (degree 1 since 12 waves per CU are resident: 0.21 vs 0.24-0.30 ms)
   bool use_rows() const
   {
-    return (rows_ok || terms_ok) && d_mtab && ((algorithm == PDH_ALG_AUTO && rows_auto) || algorithm == PDH_ALG_ROWS);
+    return row_kernel != RowKernel::none && (algorithm == PDH_ALG_AUTO || algorithm == PDH_ALG_ROWS);
   }
   // which form each of the two launches uses: [0] diagonal blocks, [1] coupling blocks
   bool use_moment(int kind) const
@@ -279,6 +287,15 @@ static int fail(pdh_ctx *ctx, int code, const std::string &msg)
     }                                                                                              \
   while (0)
 
+#define PDH_TRY(call)                                                                              \
+  do                                                                                               \
+    {                                                                                              \
+      const int rc_ = (call);                                                                      \
+      if (rc_ != PDH_OK)                                                                           \
+        return rc_;                                                                                \
+    }                                                                                              \
+  while (0)
+
 static void free_problem(pdh_ctx *ctx)
 {
   for (void *p : ctx->allocs)
@@ -288,25 +305,77 @@ static void free_problem(pdh_ctx *ctx)
   ctx->has_problem = false;
   ctx->d_ap_src = nullptr;
   ctx->d_bd_rng = nullptr;
+  ctx->d_mtab = nullptr;
+  ctx->row_kernel = RowKernel::none;
+  ctx->rows = PdhRows{};
+  ctx->terms = PdhTerms{};
 }
 
+// Device memory of set-up: `count` elements (at least one), recorded in `owner` - ctx->allocs for the resident problem (freed
+// by free_problem), Staging::bufs for the inputs of one set-up step; PDH_EDEVICE says what failed
 template <class T>
-static int upload_n(pdh_ctx *ctx, const T *h, size_t count, const T **dptr)
+static int alloc_in(pdh_ctx *ctx, std::vector<void *> &owner, size_t count, T **dptr, const char *what)
 {
   void *d = nullptr;
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  PDH_HIP(ctx, hipMalloc(&d, bytes));
-  ctx->allocs.push_back(d);
-  if (count)
-    PDH_HIP(ctx, hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice));
-  *dptr = static_cast<const T *>(d);
+  const hipError_t e = hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T));
+  if (e != hipSuccess)
+    return fail(ctx, PDH_EDEVICE, std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
+  owner.push_back(d);
+  *dptr = static_cast<T *>(d);
   return PDH_OK;
 }
-template <class V>
-static int upload(pdh_ctx *ctx, const V &h, const typename V::value_type **dptr)
+template <class T>
+static int upload_in(pdh_ctx *ctx, std::vector<void *> &owner, const T *h, size_t count, const T **dptr, const char *what)
 {
-  return upload_n(ctx, h.data(), h.size(), dptr);
+  T *d = nullptr;
+  PDH_TRY(alloc_in(ctx, owner, count, &d, what));
+  *dptr = d;
+  const hipError_t e = count ? hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+  return e == hipSuccess ? PDH_OK : fail(ctx, PDH_EDEVICE, std::string("upload (") + what + "): " + hipGetErrorString(e));
 }
+
+// persistent buffers of the resident problem
+template <class T>
+static int device_buffer(pdh_ctx *ctx, size_t count, T **dptr, const char *what)
+{
+  return alloc_in(ctx, ctx->allocs, count, dptr, what);
+}
+template <class T>
+static int upload(pdh_ctx *ctx, const T *h, size_t count, const T **dptr, const char *what)
+{
+  return upload_in(ctx, ctx->allocs, h, count, dptr, what);
+}
+template <class V>
+static int upload(pdh_ctx *ctx, const V &h, const typename V::value_type **dptr, const char *what)
+{
+  return upload_in(ctx, ctx->allocs, h.data(), h.size(), dptr, what);
+}
+#define PDH_UP(vec, field) PDH_TRY(upload(ctx, vec, &field, #field))
+
+// temporary buffers of one set-up step (the inputs of a generating / repacking kernel): freed when the step's scope ends
+struct Staging
+{
+  pdh_ctx *ctx;
+  std::vector<void *> bufs;
+  explicit Staging(pdh_ctx *c) : ctx(c) {}
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  ~Staging()
+  {
+    for (void *d : bufs)
+      (void)hipFree(d);
+  }
+  template <class T>
+  int alloc(size_t count, T **dptr, const char *what)
+  {
+    return alloc_in(ctx, bufs, count, dptr, what);
+  }
+  template <class T>
+  int upload(const T *h, size_t count, const T **dptr, const char *what)
+  {
+    return upload_in(ctx, bufs, h, count, dptr, what);
+  }
+};
 
 #ifndef PDH_SRC_HASH
 #define PDH_SRC_HASH "unhashed"
@@ -428,6 +497,7 @@ struct Packed
   std::vector<double> run_sig;
   // pdh_set_problem_cartesian: the point arrays of `src` are NULL, the points are generated on the device from these
   const pdh_cartesian_points *cart = nullptr;
+  bool ghost = false; // packed for the ghost-block exchange (PDH_EXCHANGE_GHOST)
   // host view of a packed face point (what the kernel writes): run r of the owned slots, point q of the run
   const pdh_problem *src = nullptr;
   int64_t nqf_src = 0;
@@ -616,7 +686,7 @@ static int pack_problem(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begin, i
   // A face whose sides live on different ranks is assembled by the rank that owns side 0 (the caller lists every face from
   // its owner side: the reference's `id() < neighbor->id()` rule, include/poly_utils.h:2089, 2134-2190): that rank adds
   // M11, M12 to its own rows and ships M21 (one block per face) and M22 (summed per remote polytope) to the other rank.
-  const bool ghost = exchange_mode == PDH_EXCHANGE_GHOST;
+  const bool ghost = K.ghost = exchange_mode == PDH_EXCHANGE_GHOST;
   if (ghost && K.tiled)
     return fail(ctx, PDH_EUNSUPPORTED, "more than 64 dofs per polytope run owner-computes-rows only (no ghost-block exchange)");
   int my_rank = -1, n_ranks = 1;
@@ -2069,39 +2139,111 @@ static bool build_terms_tables(const pdh_problem *p, const Packed &K, const Rows
   return true;
 }
 
-// Host-only: 1 if the row kernel (PDH_ALG_ROWS) applies to this description and row range, 0 if not (pdh_last_error(NULL)
-// says why), < 0 on an invalid description.
-extern "C" int pdh_check_rows(const pdh_problem *p, int32_t row_begin, int32_t row_end)
+// ---- which row kernel serves a problem ----------------------------------------------------------------------------------------------
+// Decided on the host, before anything of the problem goes to the device; pdh_set_problem and the pdh_check_* functions share it.
+// AUTO prefers the term kernels (pdh_terms.h; FE_DGQ(3): pdh_terms_wg.h) to the kinds of pdh_rows.h wherever both apply.
+struct KernelPlan
+{
+  RowKernel kernel = RowKernel::none;
+  RowsHost rows;  // tables of pdh_rows.h (cartesian description: what the term kernels need of them, by construction)
+  TermsHost terms;
+  int vq_n = -1;  // points per direction of the verified tensor volume rules, 0: none, -1: not looked at
+  bool tensor_only = false;
+  std::string why_rows, why_terms; // why each family refuses the problem
+};
+
+static bool env_is_zero(const char *name)
+{
+  const char *e = getenv(name);
+  return e && e[0] == '0';
+}
+
+// switches: apply the diagnostic switches of pdh_set_problem, read on every call (the tests compare the kernels in one process):
+// PDH_TERMS=0 keeps the kinds of pdh_rows.h, PDH_TERMS_DGQ3=0 keeps them for FE_DGQ(3) only.  (FE_DGQ(3) has the
+// workgroup-per-polytope form of the term kernel, pdh_terms_wg.h: the default where it applies since the records of 1-D rules and
+// the merged cells - 1.28-1.35 ms on the bench mesh where pdh_rows.h takes 1.59-1.66, never slower on the other shapes tried,
+// profiles/r04_wg_forms.txt.)  The cartesian description has no other kernel and ignores them.
+static KernelPlan plan_kernels(const pdh_problem *p, const Packed &K, bool switches)
+{
+  KernelPlan P;
+  RowsHost &RH = P.rows;
+  if (p->dim != 3 || K.n1d < 2 || K.n1d > 4)
+    {
+      P.why_rows = P.why_terms = "not 3-D FE_DGQ / FE_AggloDGP of degree 1 .. 3";
+      return P;
+    }
+  if (K.ghost)
+    {
+      P.why_rows = P.why_terms = "exchange variant";
+      return P;
+    }
+  if (K.cart)
+    { // planar axis-aligned faces and tensor rules hold by construction - and there are no host copies of the points to look at:
+      // the kinds of pdh_rows.h, whose tables are made from the points, are not offered
+      RH.planar_ok = true;
+      RH.fq_tensor_n = K.cart->nqf;
+      RH.fast_j.assign(3 * K.run_ap.size(), 0); // (the generator runs the lower tangential axis fastest)
+      P.vq_n = K.cart->nq;
+      P.why_rows = "cartesian description: the kinds of pdh_rows.h need the points";
+    }
+  else if (build_rows_tables(p, K, RH, &P.why_rows) && rows_kind_applies(p, K, RH, P.vq_n, P.tensor_only, &P.why_rows))
+    P.kernel = RowKernel::rows;
+  const int terms_kind = pdh_terms_has_kind(K.n1d, p->basis == PDH_BASIS_AGGLODGP ? 1 : 0);
+  if (!RH.planar_ok)
+    P.why_terms = P.why_rows;
+  else if (switches && !K.cart && (env_is_zero("PDH_TERMS") || (terms_kind == 2 && env_is_zero("PDH_TERMS_DGQ3"))))
+    P.why_terms = "term kernel: switched off (PDH_TERMS / PDH_TERMS_DGQ3)";
+  else
+    {
+      if (P.vq_n < 0 && RH.fq_tensor_n > 0)
+        P.vq_n = resolve_tensor_hint(p->vq_tensor_n, [&](int n) { return volume_rules_are_tensor(p, K, n); });
+      if (build_terms_tables(p, K, RH, std::max(P.vq_n, 0), P.terms, &P.why_terms))
+        P.kernel = RowKernel::terms;
+    }
+  return P;
+}
+
+static int check_plan(const pdh_problem *p, int32_t row_begin, int32_t row_end, KernelPlan &plan)
 {
   Packed K;
   g_err_noctx.clear();
-  const int rc = pack_problem(nullptr, p, row_begin, row_end, K);
-  if (rc != PDH_OK)
-    return rc;
-  RowsHost R;
-  std::string why;
-  int vq_n = 0;
-  bool tensor_only = false;
-  if (build_rows_tables(p, K, R, &why) && rows_kind_applies(p, K, R, vq_n, tensor_only, &why))
+  PDH_TRY(pack_problem(nullptr, p, row_begin, row_end, K));
+  plan = plan_kernels(p, K, false);
+  return PDH_OK;
+}
+
+// Host-only: 1 if a row kernel (PDH_ALG_ROWS: pdh_rows.h or the term kernels) applies to this description and row range, 0 if not
+// (pdh_last_error(NULL) says why), < 0 on an invalid description.
+extern "C" int pdh_check_rows(const pdh_problem *p, int32_t row_begin, int32_t row_end)
+{
+  KernelPlan plan;
+  PDH_TRY(check_plan(p, row_begin, row_end, plan));
+  if (plan.kernel != RowKernel::none)
     return 1;
-  if (R.planar_ok && R.fq_tensor_n > 0)
-    { // the term kernel (pdh_terms.h) takes the small elements on any agglomerate of Cartesian cells with tensor rules
-      std::string why_t;
-      TermsHost TH;
-      const int vn = resolve_tensor_hint(p->vq_tensor_n, [&](int n) { return volume_rules_are_tensor(p, K, n); });
-      if (vn > 0 && build_terms_tables(p, K, R, vn, TH, &why_t))
-        return 1;
-      if (!why_t.empty())
-        why += "; " + why_t;
-    }
-  g_err_noctx = why;
+  g_err_noctx = plan.why_rows;
+  if (plan.rows.planar_ok && plan.rows.fq_tensor_n > 0 && plan.vq_n > 0) // (the term kernels' own tests ran)
+    g_err_noctx += "; " + plan.why_terms;
   return 0;
 }
 
-
 // Host-only: 1 if the term kernels (pdh_terms.h / pdh_terms_wg.h) apply to this description and row range, 0 if not
-// (pdh_last_error(NULL) says why), < 0 on an invalid description.  stats4 (may be NULL): most runs / sub-faces / interior
-// sub-faces / cells of one owned polytope... and the LDS bytes of a workgroup in stats4[4].
+// (pdh_last_error(NULL) says why), < 0 on an invalid description.  stats5 (may be NULL; left alone where the faces are not unions
+// of axis-aligned planes): most runs / sub-faces / interior sub-faces / cells of one owned polytope, LDS bytes of a workgroup.
+extern "C" int pdh_check_terms(const pdh_problem *p, int32_t row_begin, int32_t row_end, int64_t *stats5)
+{
+  KernelPlan plan;
+  PDH_TRY(check_plan(p, row_begin, row_end, plan));
+  const TermsHost &TH = plan.terms;
+  if (stats5 && plan.rows.planar_ok)
+    {
+      stats5[0] = TH.maxruns, stats5[1] = TH.maxsf, stats5[2] = TH.maxsi, stats5[3] = TH.maxcell, stats5[4] = TH.lds_bytes;
+    }
+  if (plan.kernel == RowKernel::terms)
+    return 1;
+  g_err_noctx = plan.why_terms;
+  return 0;
+}
+
 // Term kernels of the resident problem: cells before / after merging, sub-faces before / after (pdh_terms_tables.h); zeros if another
 // kernel serves the problem.
 extern "C" int pdh_terms_merge_stats(pdh_ctx *ctx, int64_t *out4)
@@ -2111,36 +2253,8 @@ extern "C" int pdh_terms_merge_stats(pdh_ctx *ctx, int64_t *out4)
   if (!ctx->has_problem)
     return fail(ctx, PDH_ESTATE, "pdh_terms_merge_stats called before pdh_set_problem");
   for (int i = 0; i < 4; ++i)
-    out4[i] = ctx->terms_ok ? ctx->terms_merge[i] : 0;
+    out4[i] = ctx->row_kernel == RowKernel::terms ? ctx->terms_merge[i] : 0;
   return PDH_OK;
-}
-
-extern "C" int pdh_check_terms(const pdh_problem *p, int32_t row_begin, int32_t row_end, int64_t *stats5)
-{
-  Packed K;
-  g_err_noctx.clear();
-  const int rc = pack_problem(nullptr, p, row_begin, row_end, K);
-  if (rc != PDH_OK)
-    return rc;
-  RowsHost R;
-  std::string why;
-  (void)build_rows_tables(p, K, R, &why);
-  if (!R.planar_ok)
-    {
-      g_err_noctx = why.empty() ? std::string("term kernel: faces are not unions of axis-aligned planes") : why;
-      return 0;
-    }
-  const int vn = resolve_tensor_hint(p->vq_tensor_n, [&](int n) { return volume_rules_are_tensor(p, K, n); });
-  TermsHost TH;
-  std::string why_t;
-  const bool ok = build_terms_tables(p, K, R, vn, TH, &why_t);
-  if (stats5)
-    {
-      stats5[0] = TH.maxruns, stats5[1] = TH.maxsf, stats5[2] = TH.maxsi, stats5[3] = TH.maxcell, stats5[4] = TH.lds_bytes;
-    }
-  if (!ok)
-    g_err_noctx = why_t.empty() ? std::string("term kernel: refused (no reason recorded)") : why_t;
-  return ok ? 1 : 0;
 }
 
 // Host-only validation (no GPU needed): runs exactly the checks of pdh_set_problem.
@@ -2191,6 +2305,19 @@ extern "C" hipError_t pdh_launch_pack_faces(int dim, int64_t nqf, const double *
                                             const int32_t *pk_cnt, const int32_t *pk_flags, const double *pk_sig, int64_t nap,
                                             double *ap_x, double *ap_n, double *ap_wself, double *ap_wcross, double *ap_sig,
                                             hipStream_t stream);
+// Gauss-Legendre rule of n points on [0, 1] as the generators take it (pdh_cartgen.hip): zero-padded to PDH_MAX_N1D
+struct GaussRule01
+{
+  double x[PDH_MAX_N1D] = {0}, w[PDH_MAX_N1D] = {0};
+  explicit GaussRule01(int n)
+  {
+    std::vector<long double> gx, gw;
+    pdh::gauss_legendre01(n, gx, gw);
+    for (int i = 0; i < n; ++i)
+      x[i] = (double)gx[i], w[i] = (double)gw[i];
+  }
+};
+
 static int pack_faces_on_device(pdh_ctx *ctx, const pdh_problem *p, const Packed &K, PdhDev &D)
 {
   const int dim = p->dim;
@@ -2198,91 +2325,276 @@ static int pack_faces_on_device(pdh_ctx *ctx, const pdh_problem *p, const Packed
   double *out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const size_t out_n[5] = {(size_t)dim * nap, (size_t)dim * nap, (size_t)nap, (size_t)nap, (size_t)nap};
   for (int k = 0; k < 5; ++k)
-    {
-      void *d = nullptr;
-      PDH_HIP(ctx, hipMalloc(&d, std::max<size_t>(out_n[k], 1) * sizeof(double)));
-      ctx->allocs.push_back(d);
-      out[k] = static_cast<double *>(d);
-    }
+    PDH_TRY(device_buffer(ctx, out_n[k], &out[k], "packed face points"));
   D.ap_x = out[0], D.ap_n = out[1], D.ap_wself = out[2], D.ap_wcross = out[3], D.ap_sig = out[4];
   if (nruns == 0 || nap == 0)
     return PDH_OK;
-  std::vector<void *> tmp;
-  auto stage = [&](const void *h, size_t bytes, const void **dptr) -> hipError_t {
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, std::max<size_t>(bytes, 8));
-    if (e != hipSuccess)
-      return e;
-    tmp.push_back(d);
-    *dptr = d;
-    return bytes ? hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  };
-  const void *d_x = nullptr, *d_n = nullptr, *d_w = nullptr, *d_wo = nullptr, *d_at = nullptr, *d_fq = nullptr, *d_cnt = nullptr,
-             *d_fl = nullptr, *d_sg = nullptr;
-  hipError_t e = hipSuccess;
+  Staging st(ctx);
+  const double *d_x = nullptr, *d_n = nullptr, *d_w = nullptr, *d_wo = nullptr;
   if (K.cart)
     { // the caller-order face arrays are generated here from (cell, local face) of every sub-face (pdh_cartgen.hip); JxW of side 1
       // equals JxW of side 0 on a conforming Cartesian grid (d_wo stays NULL)
       const pdh_cartesian_points *cp = K.cart;
       const int64_t nsf = nqf / ((int64_t)cp->nqf * cp->nqf);
-      std::vector<long double> gx, gw;
-      pdh::gauss_legendre01(cp->nqf, gx, gw);
-      double nodes[PDH_MAX_N1D] = {0}, weights[PDH_MAX_N1D] = {0};
-      for (int i = 0; i < cp->nqf; ++i)
-        nodes[i] = (double)gx[i], weights[i] = (double)gw[i];
-      const void *d_box = nullptr, *d_cell = nullptr, *d_face = nullptr;
-      auto alloc = [&](size_t bytes, const void **dptr) -> hipError_t {
-        void *d = nullptr;
-        hipError_t e_ = hipMalloc(&d, std::max<size_t>(bytes, 8));
-        if (e_ == hipSuccess)
-          tmp.push_back(d), *dptr = d;
-        return e_;
-      };
-      e = stage(cp->cell_box, (size_t)cp->n_cells * 6 * sizeof(double), &d_box);
-      if (e == hipSuccess)
-        e = stage(cp->fq_cell, (size_t)nsf * sizeof(int32_t), &d_cell);
-      if (e == hipSuccess)
-        e = stage(cp->fq_face, (size_t)nsf * sizeof(int32_t), &d_face);
-      if (e == hipSuccess)
-        e = alloc((size_t)dim * nqf * sizeof(double), &d_x);
-      if (e == hipSuccess)
-        e = alloc((size_t)dim * nqf * sizeof(double), &d_n);
-      if (e == hipSuccess)
-        e = alloc((size_t)nqf * sizeof(double), &d_w);
-      if (e == hipSuccess)
-        e = pdh_launch_gen_faces(cp->nqf, nodes, weights, (const double *)d_box, (const int32_t *)d_cell, (const int32_t *)d_face, nqf,
-                                 (double *)d_x, (double *)d_n, (double *)d_w, ctx->stream);
+      const double *d_box = nullptr;
+      const int32_t *d_cell = nullptr, *d_face = nullptr;
+      double *x = nullptr, *n = nullptr, *w = nullptr;
+      PDH_TRY(st.upload(cp->cell_box, (size_t)cp->n_cells * 6, &d_box, "cell boxes"));
+      PDH_TRY(st.upload(cp->fq_cell, (size_t)nsf, &d_cell, "cells of the sub-faces"));
+      PDH_TRY(st.upload(cp->fq_face, (size_t)nsf, &d_face, "local faces of the sub-faces"));
+      PDH_TRY(st.alloc((size_t)dim * nqf, &x, "face points"));
+      PDH_TRY(st.alloc((size_t)dim * nqf, &n, "face normals"));
+      PDH_TRY(st.alloc((size_t)nqf, &w, "face weights"));
+      const GaussRule01 g(cp->nqf);
+      PDH_HIP(ctx, pdh_launch_gen_faces(cp->nqf, g.x, g.w, d_box, d_cell, d_face, nqf, x, n, w, ctx->stream));
+      d_x = x, d_n = n, d_w = w;
     }
   else
     {
-      e = stage(p->fq_x, (size_t)dim * nqf * sizeof(double), &d_x);
-      if (e == hipSuccess)
-        e = stage(p->fq_n, (size_t)dim * nqf * sizeof(double), &d_n);
-      if (e == hipSuccess)
-        e = stage(p->fq_w, (size_t)nqf * sizeof(double), &d_w);
-      if (e == hipSuccess && p->fq_w_out)
-        e = stage(p->fq_w_out, (size_t)nqf * sizeof(double), &d_wo);
+      PDH_TRY(st.upload(p->fq_x, (size_t)dim * nqf, &d_x, "face points"));
+      PDH_TRY(st.upload(p->fq_n, (size_t)dim * nqf, &d_n, "face normals"));
+      PDH_TRY(st.upload(p->fq_w, (size_t)nqf, &d_w, "face weights"));
+      if (p->fq_w_out)
+        PDH_TRY(st.upload(p->fq_w_out, (size_t)nqf, &d_wo, "face weights of side 1"));
     }
-  if (e == hipSuccess)
-    e = stage(K.pk_at.data(), K.pk_at.size() * sizeof(int64_t), &d_at);
-  if (e == hipSuccess)
-    e = stage(K.pk_fq.data(), K.pk_fq.size() * sizeof(int64_t), &d_fq);
-  if (e == hipSuccess)
-    e = stage(K.pk_cnt.data(), K.pk_cnt.size() * sizeof(int32_t), &d_cnt);
-  if (e == hipSuccess)
-    e = stage(K.pk_flags.data(), K.pk_flags.size() * sizeof(int32_t), &d_fl);
-  if (e == hipSuccess)
-    e = stage(K.pk_sig.data(), K.pk_sig.size() * sizeof(double), &d_sg);
-  if (e == hipSuccess)
-    e = pdh_launch_pack_faces(dim, nqf, (const double *)d_x, (const double *)d_n, (const double *)d_w, (const double *)d_wo, nruns,
-                              (const int64_t *)d_at, (const int64_t *)d_fq, (const int32_t *)d_cnt, (const int32_t *)d_fl,
-                              (const double *)d_sg, nap, out[0], out[1], out[2], out[3], out[4], ctx->stream);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(ctx->stream);
-  for (void *d : tmp)
-    (void)hipFree(d);
-  if (e != hipSuccess)
-    return fail(ctx, PDH_EDEVICE, std::string("face repack: ") + hipGetErrorString(e));
+  const int64_t *d_at = nullptr, *d_fq = nullptr;
+  const int32_t *d_cnt = nullptr, *d_fl = nullptr;
+  const double *d_sg = nullptr;
+  PDH_TRY(st.upload(K.pk_at.data(), K.pk_at.size(), &d_at, "face runs: packed position"));
+  PDH_TRY(st.upload(K.pk_fq.data(), K.pk_fq.size(), &d_fq, "face runs: caller position"));
+  PDH_TRY(st.upload(K.pk_cnt.data(), K.pk_cnt.size(), &d_cnt, "face runs: counts"));
+  PDH_TRY(st.upload(K.pk_flags.data(), K.pk_flags.size(), &d_fl, "face runs: flags"));
+  PDH_TRY(st.upload(K.pk_sig.data(), K.pk_sig.size(), &d_sg, "face runs: sigma"));
+  PDH_HIP(ctx, pdh_launch_pack_faces(dim, nqf, d_x, d_n, d_w, d_wo, nruns, d_at, d_fq, d_cnt, d_fl, d_sg, nap, out[0], out[1], out[2],
+                                     out[3], out[4], ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PDH_OK;
+}
+
+// pdh_set_problem_cartesian: the volume points of the owned slots, generated slot by slot from the cells' boxes (pdh_cartgen.hip)
+static int generate_volume_points(pdh_ctx *ctx, const Packed &K, PdhDev &D)
+{
+  const pdh_cartesian_points *cart = K.cart;
+  const int64_t m3 = (int64_t)cart->nq * cart->nq * cart->nq, ngroups = K.n_vq / m3;
+  std::vector<int32_t> gcell((size_t)std::max<int64_t>(ngroups, 1));
+  for (int sl = 0; sl < K.n_owned; ++sl)
+    {
+      const int64_t g0 = K.vq_ptr[sl] / m3, g1 = K.vq_ptr[sl + 1] / m3, src = K.vq_src[sl] / m3;
+      for (int64_t g = g0; g < g1; ++g)
+        gcell[(size_t)g] = cart->vq_cell[src + (g - g0)];
+    }
+  double *x = nullptr, *w = nullptr;
+  PDH_TRY(device_buffer(ctx, (size_t)3 * K.n_vq, &x, "volume points"));
+  PDH_TRY(device_buffer(ctx, (size_t)K.n_vq, &w, "volume weights"));
+  Staging st(ctx);
+  const double *d_box = nullptr;
+  const int32_t *d_gcell = nullptr;
+  PDH_TRY(st.upload(cart->cell_box, (size_t)cart->n_cells * 6, &d_box, "cell boxes"));
+  PDH_TRY(st.upload(gcell.data(), gcell.size(), &d_gcell, "cells of the volume rules"));
+  const GaussRule01 g(cart->nq);
+  PDH_HIP(ctx, pdh_launch_gen_volume(cart->nq, g.x, g.w, d_box, d_gcell, K.n_vq, x, K.n_vq, w, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  D.vq_x = x, D.vq_w = w;
+  return PDH_OK;
+}
+
+// Device state every kernel reads: boxes, points, faces, the maps of the blocks, the values (with the send region of the
+// ghost-block exchange behind them), the moment tables (3-D, degree 1 .. 3).
+static int upload_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
+{
+  PdhDev &D = ctx->dev;
+  std::memset(&D, 0, sizeof(D));
+  D.dim = p->dim;
+  D.n = K.n;
+  D.n1d = K.n1d;
+  D.diag_first = p->diag_first ? 1 : 0;
+  D.reaction_c = p->reaction_c;
+  D.tab = K.tab;
+  D.vq_stride = K.vq_stride_h;
+  D.ap_stride = K.n_ap;
+  const std::vector<double> bbox(p->bbox, p->bbox + (size_t)p->n_agg * 2 * p->dim);
+  PDH_UP(bbox, D.bbox);
+  PDH_UP(K.midx, D.midx);
+  PDH_UP(K.vq_ptr, D.vq_ptr);
+  if (K.cart)
+    PDH_TRY(generate_volume_points(ctx, K, D));
+  else
+    {
+      PDH_TRY(upload(ctx, K.vqx_h, (size_t)p->dim * K.vq_stride_h, &D.vq_x, "D.vq_x"));
+      PDH_TRY(upload(ctx, K.vqw_h, (size_t)K.n_vq, &D.vq_w, "D.vq_w"));
+    }
+  PDH_UP(K.ap_ptr, D.ap_ptr);
+  PDH_TRY(pack_faces_on_device(ctx, p, K, D));
+  PDH_UP(K.own_agg, D.own_agg);
+  PDH_UP(K.own_row, D.own_row);
+  PDH_UP(K.row_base, D.row_base);
+  PDH_UP(K.row_len, D.row_len);
+  PDH_UP(K.diag_L, D.diag_L);
+  PDH_UP(K.it_own, D.it_own);
+  PDH_UP(K.it_nbr, D.it_nbr);
+  PDH_UP(K.it_pbeg, D.it_pbeg);
+  PDH_UP(K.it_pcnt, D.it_pcnt);
+  PDH_UP(K.it_pos, D.it_pos);
+  PDH_UP(K.it_nbr_slot, D.it_nbr_slot);
+  PDH_UP(K.it_pos_t, D.it_pos_t);
+  if (K.ghost)
+    {
+      PDH_UP(K.r21_src, ctx->d_r21_src);
+      PDH_UP(K.r21_dst, ctx->d_r21_dst);
+      PDH_UP(K.r21_rlen, ctx->d_r21_rlen);
+      PDH_UP(K.r22_ptr, ctx->d_r22_ptr);
+      PDH_UP(K.r22_src, ctx->d_r22_src);
+      PDH_UP(K.r22_slot, ctx->d_r22_slot);
+    }
+  PDH_TRY(device_buffer(ctx, (size_t)(K.n_values + K.n_send), &D.values, "values"));
+  // (the per-point map of the packed boundary points to the caller's face points - 8 bytes per packed face point - is needed by
+  // the right-hand side only: built and uploaded at its first call, ensure_ap_src)
+  PDH_UP(K.vq_src, ctx->d_vq_src);
+  if (p->dim == 3 && K.n1d >= 2 && K.n1d <= 4)
+    {
+      const std::vector<double> mt = pdh::moment_tables(p->degree, p->basis);
+      if ((int)mt.size() != pdh_moment_table_doubles(K.n1d))
+        return fail(ctx, PDH_EDEVICE, "moment tables: the host's and the kernels' sizes differ");
+      PDH_UP(mt, ctx->d_mtab);
+    }
+  return PDH_OK;
+}
+
+// Host side of the resident problem: sizes, the caller-order maps of the right-hand side, the kernels' launch shapes and work.
+static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
+{
+  ctx->problem_ghost = K.ghost;
+  ctx->n_send = K.n_send;
+  ctx->n_recv = K.n_recv;
+  ctx->send_count = K.send_count;
+  ctx->recv_count = K.recv_count;
+  ctx->n_r21 = (int)K.r21_src.size();
+  ctx->n_r22 = (int)K.r22_slot.size();
+  ctx->n_values = K.n_values;
+  ctx->n_owned = K.n_owned;
+  ctx->n_diag_slots = (int)K.own_agg.size();
+  ctx->n_items = (int)K.it_own.size();
+  ctx->n_vq = K.n_vq;
+  ctx->n_ap = K.n_ap;
+  ctx->NT = K.NT;
+  ctx->LB = K.LB;
+  ctx->tiled = K.tiled;
+  ctx->group = K.tiled ? -1 : combo_group(p->dim, K.n1d, K.NT, K.LB);
+  ctx->lds_diag = pdh::lds_bytes_diag(p->dim, K.n1d, K.NT);
+  ctx->lds_off = pdh::lds_bytes_offdiag(p->dim, K.n1d, K.NT);
+  ctx->basis = p->basis;
+  ctx->vq_src = K.vq_src;
+  ctx->n_vq_caller = p->vq_ptr[p->n_agg];
+  ctx->n_fq_caller = p->n_faces ? p->fq_ptr[p->n_faces] : 0;
+  ctx->face_runs.clear();
+  ctx->face_runs.reserve(K.run_ap.size());
+  for (size_t r = 0; r < K.run_ap.size(); ++r)
+    ctx->face_runs.push_back({K.run_ap[r], K.run_fq[r], K.run_cnt[r], K.run_bdry[r], K.run_slot[r]});
+  ctx->n_rows_owned = (int64_t)K.n_owned * K.n;
+  ctx->n_agg_total = p->n_agg;
+  // executed work: k-steps of 4 points per chunk (64 points in k_diag for NT >= 3, else 32; 32 in k_offdiag)
+  const int64_t i_sym = sched_instr_rt(K.NT, K.LB, true), i_full = sched_instr_rt(K.NT, K.LB, false);
+  const int ch_d = (K.NT >= 3) ? 64 : 32, ch_o = 32;
+  auto ksteps = [](int64_t npts, int ch) {
+    int64_t s = (npts / ch) * (ch / 4);
+    const int64_t rem = npts % ch;
+    return s + (rem + 3) / 4;
+  };
+  int64_t kv = 0, kf = 0, ko = 0;
+  for (size_t sl = 0; sl < K.own_agg.size(); ++sl)
+    {
+      kv += ksteps(K.vq_ptr[sl + 1] - K.vq_ptr[sl], ch_d);
+      kf += ksteps(K.ap_ptr[sl + 1] - K.ap_ptr[sl], ch_d);
+    }
+  for (size_t it = 0; it < K.it_pcnt.size(); ++it)
+    ko += ksteps(K.it_pcnt[it], ch_o);
+  ctx->mfma_diag = kv * (p->dim + (p->reaction_c != 0.0 ? 1 : 0)) * i_sym + kf * 2 * i_sym;
+  ctx->mfma_offdiag = ko * 2 * i_full;
+  if (K.tiled)
+    { // tiles ti < tj of the own block and all tiles of a coupling block are full 64 x 64 products (64 instructions per k-step), the
+      // tiles ti == tj symmetric ones (the schedule of a full n = 64 block)
+      const int64_t nt = (K.n + 63) / 64, i64 = sched_instr_rt(4, 4, true);
+      ctx->mfma_diag = (kv * (p->dim + (p->reaction_c != 0.0 ? 1 : 0)) + kf * 2) * (64 * (nt * (nt - 1) / 2) + i64 * nt);
+      ctx->mfma_offdiag = ko * 2 * 64 * nt * nt;
+    }
+}
+
+// pdh_rows.h: face tables and per-slot records, the work counter of the persistent waves, the stamps of -DPDHR_STAMP builds and,
+// for the MULTI instantiation, a scratch row per resident wave
+static int upload_rows_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &plan)
+{
+  const RowsHost &RH = plan.rows;
+  PdhRows &R = ctx->rows;
+  PDH_UP(RH.fr_ptr, R.fr_ptr);
+  PDH_UP(RH.fr_pbeg, R.fr_pbeg);
+  PDH_UP(RH.fr_pcnt, R.fr_pcnt);
+  PDH_UP(RH.fr_nbr, R.fr_nbr);
+  PDH_UP(RH.fr_axis, R.fr_axis);
+  PDH_UP(RH.fr_blk, R.fr_blk);
+  PDH_UP(RH.fr_flags, R.fr_flags);
+  PDH_UP(RH.fr_coord, R.fr_coord);
+  PDH_UP(RH.fr_sigma, R.fr_sigma);
+  PDH_UP(RH.fr_nsign, R.fr_nsign);
+  PDH_UP(RH.meta, R.meta);
+  PDH_TRY(device_buffer(ctx, 16, &R.sched, "row kernel: work counter"));
+  PDH_HIP(ctx, hipMemset(R.sched, 0, 16 * sizeof(unsigned int)));
+  const size_t n_stamps = (size_t)std::max(K.n_owned, 1) * 16;
+  PDH_TRY(device_buffer(ctx, n_stamps, &R.stamps, "row kernel: stamps"));
+  PDH_HIP(ctx, hipMemset(R.stamps, 0, n_stamps * sizeof(long long)));
+  if (RH.multi)
+    {
+      // MULTI instantiation: the coupling moments of a polytope's interior entries (8 x 8 doubles each, up to 40 of
+      // them) are parked between P2 and P5 in a per-wave row of this buffer instead of LDS (pdh_rows.h) - 8 waves per
+      // CU at most (256 VGPRs), a few tens of MB that stay in L2 / the memory-side cache
+      int cus = 256;
+      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+      const int waves = cus * 8;
+      // (with tensor sub-face rules the row holds 16 + 16 factors per interior sub-face instead, pdh_rows.h: FACT)
+      const size_t stride = std::max<size_t>((size_t)RH.maxf * 64, (size_t)RH.maxs * 32 + 64);
+      PDH_TRY(device_buffer(ctx, (size_t)waves * stride, &R.m2c_scratch, "row kernel: MULTI scratch"));
+      R.scratch_waves = waves;
+      R.scratch_stride = (int64_t)stride;
+    }
+  R.tensor_only = plan.tensor_only ? 1 : 0;
+  R.multi = RH.multi ? 1 : 0;
+  R.maxe = RH.maxe;
+  R.maxf = RH.maxf;
+  R.vq_tensor_n = plan.vq_n;
+  R.fq_tensor_n = RH.fq_tensor_n;
+  return PDH_OK;
+}
+
+// Term kernels: their tables, the records of 1-D rules the kernels read (gathered on the device from the point arrays), the
+// stamps of -DPDHT_STAMP builds
+static int upload_terms_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &plan)
+{
+  const TermsHost &TH = plan.terms;
+  PdhTerms &T = ctx->terms;
+  PDH_UP(TH.meta, T.meta);
+  PDH_UP(TH.sf_pt, T.sf_pt);
+  PDH_UP(TH.sf_info, T.sf_info);
+  PDH_UP(TH.sf_ivl, T.sf_ivl);
+  PDH_UP(TH.cell_ivl, T.cell_ivl);
+  T.maxruns = TH.maxruns, T.maxsf = TH.maxsf, T.maxsi = TH.maxsi, T.maxcell = TH.maxcell;
+  T.vq_tensor_n = plan.vq_n, T.fq_tensor_n = plan.rows.fq_tensor_n;
+  T.lds_bytes = TH.lds_bytes;
+  T.split = TH.split;
+  T.task_pts = TH.task_pts;
+  // the 1-D rules the kernels read, gathered on the device from the point arrays (zero-filled: slots behind a rule)
+  T.tpm = TH.task_pts > 4 ? 8 : 4;
+  T.tstride = pdh_terms_task_doubles(T.maxsf, T.maxcell, T.tpm);
+  const size_t n_tdata = (size_t)std::max(K.n_owned, 1) * T.tstride;
+  double *tdata = nullptr;
+  PDH_TRY(device_buffer(ctx, n_tdata, &tdata, "term kernel: records of 1-D rules"));
+  PDH_HIP(ctx, hipMemsetAsync(tdata, 0, n_tdata * sizeof(double), ctx->stream));
+  T.tdata = tdata;
+  PDH_HIP(ctx, pdh_launch_terms_gather(&ctx->dev, &T, tdata, K.n_owned, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t n_stamps = (size_t)std::max(K.n_owned, 1) * 16;
+  PDH_TRY(device_buffer(ctx, n_stamps, &T.stamps, "term kernel: stamps"));
+  PDH_HIP(ctx, hipMemset(T.stamps, 0, n_stamps * sizeof(long long)));
+  ctx->terms_merge[0] = TH.n_cells_in, ctx->terms_merge[1] = TH.n_cells_out;
+  ctx->terms_merge[2] = TH.n_sf_in, ctx->terms_merge[3] = TH.n_sf_out;
   return PDH_OK;
 }
 
@@ -2310,6 +2622,16 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_problem(ctx);
+  struct FreeUnlessDone // every exit before the end leaves no problem resident
+  {
+    pdh_ctx *ctx;
+    bool done = false;
+    ~FreeUnlessDone()
+    {
+      if (!done)
+        free_problem(ctx);
+    }
+  } guard{ctx};
   // PDH_TRACE_SETUP=1 (diagnostics): wall time of the phases of this call on stderr
   static const bool trace = getenv("PDH_TRACE_SETUP") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
@@ -2317,401 +2639,42 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
     if (!trace)
       return;
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[pdh_set_problem] %-28s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    fprintf(stderr, "[pdh_set_problem] %-32s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
   lap("wait for the stream, free the old problem");
+
+  // 1. host: validate and repack, choose the row kernel
   std::unique_ptr<Packed> K_owner(new Packed);
   Packed &K = *K_owner;
-  int rc = pack_problem(ctx, p, row_begin, row_end, K, ctx->exchange_mode, cart);
-  if (rc != PDH_OK)
-    return rc;
+  PDH_TRY(pack_problem(ctx, p, row_begin, row_end, K, ctx->exchange_mode, cart));
   lap("validate + repack (host)");
-
-  PdhDev &D = ctx->dev;
-  std::memset(&D, 0, sizeof(D));
-  D.dim = p->dim;
-  D.n = K.n;
-  D.n1d = K.n1d;
-  D.diag_first = p->diag_first ? 1 : 0;
-  D.reaction_c = p->reaction_c;
-  D.tab = K.tab;
-  std::vector<double> bbox(p->bbox, p->bbox + (size_t)p->n_agg * 2 * p->dim);
-#define PDH_UP(vec, field)                                                                         \
-  if ((rc = upload(ctx, vec, &D.field)) != PDH_OK)                                                 \
-    {                                                                                              \
-      free_problem(ctx);                                                                           \
-      return rc;                                                                                   \
-    }
-  PDH_UP(bbox, bbox)
-  PDH_UP(K.midx, midx)
-  PDH_UP(K.vq_ptr, vq_ptr)
-  if (cart)
-    { // volume points: generated slot by slot from the cells' boxes (pdh_cartgen.hip)
-      const int64_t m3 = (int64_t)cart->nq * cart->nq * cart->nq, ngroups = K.n_vq / m3;
-      std::vector<int32_t> gcell((size_t)std::max<int64_t>(ngroups, 1));
-      for (int sl = 0; sl < K.n_owned; ++sl)
-        {
-          const int64_t g0 = K.vq_ptr[sl] / m3, g1 = K.vq_ptr[sl + 1] / m3, src = K.vq_src[sl] / m3;
-          for (int64_t g = g0; g < g1; ++g)
-            gcell[(size_t)g] = cart->vq_cell[src + (g - g0)];
-        }
-      std::vector<long double> gx, gw;
-      pdh::gauss_legendre01(cart->nq, gx, gw);
-      double nodes[PDH_MAX_N1D] = {0}, weights[PDH_MAX_N1D] = {0};
-      for (int i = 0; i < cart->nq; ++i)
-        nodes[i] = (double)gx[i], weights[i] = (double)gw[i];
-      void *dx = nullptr, *dw = nullptr, *dbox = nullptr, *dgc = nullptr;
-      hipError_t eg = hipMalloc(&dx, std::max<size_t>((size_t)3 * K.n_vq, 1) * sizeof(double));
-      if (eg == hipSuccess)
-        {
-          ctx->allocs.push_back(dx);
-          eg = hipMalloc(&dw, std::max<size_t>((size_t)K.n_vq, 1) * sizeof(double));
-        }
-      if (eg == hipSuccess)
-        {
-          ctx->allocs.push_back(dw);
-          eg = hipMalloc(&dbox, (size_t)cart->n_cells * 6 * sizeof(double));
-        }
-      if (eg == hipSuccess)
-        eg = hipMalloc(&dgc, gcell.size() * sizeof(int32_t));
-      if (eg == hipSuccess)
-        eg = hipMemcpy(dbox, cart->cell_box, (size_t)cart->n_cells * 6 * sizeof(double), hipMemcpyHostToDevice);
-      if (eg == hipSuccess)
-        eg = hipMemcpy(dgc, gcell.data(), gcell.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-      if (eg == hipSuccess)
-        eg = pdh_launch_gen_volume(cart->nq, nodes, weights, (const double *)dbox, (const int32_t *)dgc, K.n_vq, (double *)dx, K.n_vq,
-                                   (double *)dw, ctx->stream);
-      if (eg == hipSuccess)
-        eg = hipStreamSynchronize(ctx->stream);
-      if (dbox)
-        (void)hipFree(dbox);
-      if (dgc)
-        (void)hipFree(dgc);
-      if (eg != hipSuccess)
-        {
-          free_problem(ctx);
-          return fail(ctx, PDH_EDEVICE, std::string("cartesian description: ") + hipGetErrorString(eg));
-        }
-      D.vq_x = static_cast<const double *>(dx);
-      D.vq_w = static_cast<const double *>(dw);
-    }
-  else if ((rc = upload_n(ctx, K.vqx_h, (size_t)p->dim * K.vq_stride_h, &D.vq_x)) != PDH_OK ||
-           (rc = upload_n(ctx, K.vqw_h, (size_t)K.n_vq, &D.vq_w)) != PDH_OK)
+  auto plan = std::make_unique<KernelPlan>(plan_kernels(p, K, true));
+  lap("row kernel plan (host)");
+  if (cart && plan->kernel != RowKernel::terms)
+    return fail(ctx, PDH_EUNSUPPORTED, "cartesian description: the term kernels do not apply (a polytope's tables exceed their LDS budget, "
+                                       "or the element has none): describe the problem with its points (pdh_set_problem)");
+  // 2. device: the state every kernel reads
+  PDH_TRY(upload_problem(ctx, p, K));
+  record_problem(ctx, p, K);
+  lap("upload: state of every kernel");
+  // 3. device: the state of the row kernel the plan chose, of that one only
+  if (plan->kernel == RowKernel::rows)
     {
-      free_problem(ctx);
-      return rc;
+      PDH_TRY(upload_rows_state(ctx, K, *plan));
+      lap("upload: pdh_rows.h state");
     }
-  PDH_UP(K.ap_ptr, ap_ptr)
-  if ((rc = pack_faces_on_device(ctx, p, K, D)) != PDH_OK)
+  else if (plan->kernel == RowKernel::terms)
     {
-      free_problem(ctx);
-      return rc;
+      PDH_TRY(upload_terms_state(ctx, K, *plan));
+      lap("upload: term kernel state");
     }
-  PDH_UP(K.own_agg, own_agg)
-  PDH_UP(K.own_row, own_row)
-  PDH_UP(K.row_base, row_base)
-  PDH_UP(K.row_len, row_len)
-  PDH_UP(K.diag_L, diag_L)
-  PDH_UP(K.it_own, it_own)
-  PDH_UP(K.it_nbr, it_nbr)
-  PDH_UP(K.it_pbeg, it_pbeg)
-  PDH_UP(K.it_pcnt, it_pcnt)
-  PDH_UP(K.it_pos, it_pos)
-  PDH_UP(K.it_nbr_slot, it_nbr_slot)
-  PDH_UP(K.it_pos_t, it_pos_t)
-#undef PDH_UP
-  lap("upload");
-  ctx->problem_ghost = ctx->exchange_mode == PDH_EXCHANGE_GHOST;
-  ctx->n_send = K.n_send;
-  ctx->n_recv = K.n_recv;
-  ctx->send_count = K.send_count;
-  ctx->recv_count = K.recv_count;
-  ctx->n_r21 = (int)K.r21_src.size();
-  ctx->n_r22 = (int)K.r22_slot.size();
-  if (ctx->problem_ghost)
-    {
-      if ((rc = upload(ctx, K.r21_src, &ctx->d_r21_src)) != PDH_OK || (rc = upload(ctx, K.r21_dst, &ctx->d_r21_dst)) != PDH_OK ||
-          (rc = upload(ctx, K.r21_rlen, &ctx->d_r21_rlen)) != PDH_OK || (rc = upload(ctx, K.r22_ptr, &ctx->d_r22_ptr)) != PDH_OK ||
-          (rc = upload(ctx, K.r22_src, &ctx->d_r22_src)) != PDH_OK || (rc = upload(ctx, K.r22_slot, &ctx->d_r22_slot)) != PDH_OK)
-        {
-          free_problem(ctx);
-          return rc;
-        }
-    }
-  D.vq_stride = K.vq_stride_h;
-  D.ap_stride = K.n_ap;
-  void *dv = nullptr;
-  // the send region of the ghost-block exchange sits behind the values: the kernels address it like more rows
-  hipError_t e = hipMalloc(&dv, std::max<int64_t>(K.n_values + K.n_send, 1) * sizeof(double));
-  if (e != hipSuccess)
-    {
-      free_problem(ctx);
-      return fail(ctx, PDH_EDEVICE, std::string("hipMalloc(values): ") + hipGetErrorString(e));
-    }
-  ctx->allocs.push_back(dv);
-  D.values = static_cast<double *>(dv);
-  ctx->n_values = K.n_values;
-  ctx->n_owned = K.n_owned;
-  ctx->n_diag_slots = (int)K.own_agg.size();
-  ctx->n_items = (int)K.it_own.size();
-  ctx->n_vq = K.n_vq;
-  ctx->n_ap = K.n_ap;
-  ctx->NT = K.NT;
-  ctx->LB = K.LB;
-  ctx->tiled = K.tiled;
-  ctx->group = K.tiled ? -1 : combo_group(p->dim, K.n1d, K.NT, K.LB);
-  ctx->lds_diag = pdh::lds_bytes_diag(p->dim, K.n1d, K.NT);
-  ctx->lds_off = pdh::lds_bytes_offdiag(p->dim, K.n1d, K.NT);
-  lap("values allocation");
-  ctx->vq_src = K.vq_src;
-  {
-    // (the per-point map of the packed boundary points to the caller's face points - 8 bytes per packed face point - is
-    // needed by the right-hand side only: built and uploaded at its first call, ensure_ap_src)
-    ctx->d_ap_src = nullptr;
-    if ((rc = upload(ctx, K.vq_src, &ctx->d_vq_src)) != PDH_OK)
-      {
-        free_problem(ctx);
-        return rc;
-      }
-    ctx->n_vq_caller = p->vq_ptr[p->n_agg];
-    ctx->n_fq_caller = p->n_faces ? p->fq_ptr[p->n_faces] : 0;
-  }
-  ctx->face_runs.clear();
-  ctx->face_runs.reserve(K.run_ap.size());
-  for (size_t r = 0; r < K.run_ap.size(); ++r)
-    ctx->face_runs.push_back({K.run_ap[r], K.run_fq[r], K.run_cnt[r], K.run_bdry[r], K.run_slot[r]});
-  lap("caller-order maps");
-  ctx->n_rows_owned = (int64_t)K.n_owned * K.n;
-  ctx->n_agg_total = p->n_agg;
-  {
-    // executed work: k-steps of 4 points per chunk (64 points in k_diag for NT >= 3, else 32; 32 in k_offdiag)
-    const int64_t i_sym = sched_instr_rt(K.NT, K.LB, true), i_full = sched_instr_rt(K.NT, K.LB, false);
-    const int ch_d = (K.NT >= 3) ? 64 : 32, ch_o = 32;
-    auto ksteps = [](int64_t npts, int ch) {
-      int64_t s = (npts / ch) * (ch / 4);
-      const int64_t rem = npts % ch;
-      return s + (rem + 3) / 4;
-    };
-    int64_t kv = 0, kf = 0, ko = 0;
-    for (size_t sl = 0; sl < K.own_agg.size(); ++sl)
-      {
-        kv += ksteps(K.vq_ptr[sl + 1] - K.vq_ptr[sl], ch_d);
-        kf += ksteps(K.ap_ptr[sl + 1] - K.ap_ptr[sl], ch_d);
-      }
-    for (size_t it = 0; it < K.it_pcnt.size(); ++it)
-      ko += ksteps(K.it_pcnt[it], ch_o);
-    ctx->mfma_diag = kv * (p->dim + (p->reaction_c != 0.0 ? 1 : 0)) * i_sym + kf * 2 * i_sym;
-    ctx->mfma_offdiag = ko * 2 * i_full;
-    if (K.tiled)
-      { // tiles ti < tj of the own block and all tiles of a coupling block are full 64 x 64 products (64 instructions per k-step), the
-        // tiles ti == tj symmetric ones (the schedule of a full n = 64 block)
-        const int64_t nt = (K.n + 63) / 64, i64 = sched_instr_rt(4, 4, true);
-        ctx->mfma_diag = (kv * (p->dim + (p->reaction_c != 0.0 ? 1 : 0)) + kf * 2) * (64 * (nt * (nt - 1) / 2) + i64 * nt);
-        ctx->mfma_offdiag = ko * 2 * 64 * nt * nt;
-      }
-  }
-  ctx->basis = p->basis;
-  ctx->d_mtab = nullptr;
-  if (p->dim == 3 && K.n1d >= 2 && K.n1d <= 4)
-    {
-      const std::vector<double> mt = pdh::moment_tables(p->degree, p->basis);
-      void *dm = nullptr;
-      hipError_t em = (int)mt.size() == pdh_moment_table_doubles(K.n1d) ? hipMalloc(&dm, mt.size() * sizeof(double)) : hipErrorInvalidValue;
-      if (em == hipSuccess)
-        {
-          ctx->allocs.push_back(dm);
-          em = hipMemcpy(dm, mt.data(), mt.size() * sizeof(double), hipMemcpyHostToDevice);
-        }
-      if (em != hipSuccess)
-        {
-          free_problem(ctx);
-          return fail(ctx, PDH_EDEVICE, std::string("moment tables: ") + hipGetErrorString(em));
-        }
-      ctx->d_mtab = static_cast<double *>(dm);
-    }
-  lap("values + tables");
-  ctx->rows_ok = false;
-  ctx->terms_ok = false;
-  if (ctx->d_mtab && !ctx->problem_ghost)
-    {
-      RowsHost RH;
-      // (cartesian description: planar axis-aligned faces and tensor rules hold by construction - and there are no host copies of
-      // the points to look at: the kinds of pdh_rows.h, whose tables are made from the points, are not offered)
-      const bool rows_built = cart ? false : build_rows_tables(p, K, RH);
-      int vq_n_terms = -1; // (not looked at yet)
-      if (cart)
-        {
-          RH.planar_ok = true;
-          RH.fq_tensor_n = cart->nqf;
-          RH.fast_j.assign(3 * K.run_ap.size(), 0); // (the generator runs the lower tangential axis fastest)
-          vq_n_terms = cart->nq;
-        }
-      if (rows_built)
-        {
-          lap("row kernel: planes + records");
-          PdhRows &R = ctx->rows;
-          if ((rc = upload(ctx, RH.fr_ptr, &R.fr_ptr)) != PDH_OK || (rc = upload(ctx, RH.fr_pbeg, &R.fr_pbeg)) != PDH_OK ||
-              (rc = upload(ctx, RH.fr_pcnt, &R.fr_pcnt)) != PDH_OK || (rc = upload(ctx, RH.fr_nbr, &R.fr_nbr)) != PDH_OK ||
-              (rc = upload(ctx, RH.fr_axis, &R.fr_axis)) != PDH_OK || (rc = upload(ctx, RH.fr_blk, &R.fr_blk)) != PDH_OK ||
-              (rc = upload(ctx, RH.fr_flags, &R.fr_flags)) != PDH_OK ||
-              (rc = upload(ctx, RH.fr_coord, &R.fr_coord)) != PDH_OK || (rc = upload(ctx, RH.fr_sigma, &R.fr_sigma)) != PDH_OK ||
-              (rc = upload(ctx, RH.fr_nsign, &R.fr_nsign)) != PDH_OK || (rc = upload(ctx, RH.meta, &R.meta)) != PDH_OK)
-            {
-              free_problem(ctx);
-              return rc;
-            }
-          {
-            void *dq = nullptr;
-            if (hipMalloc(&dq, 64) != hipSuccess)
-              {
-                free_problem(ctx);
-                return fail(ctx, PDH_EDEVICE, "row kernel: out of device memory");
-              }
-            ctx->allocs.push_back(dq);
-            if (hipMemset(dq, 0, 64) != hipSuccess)
-              {
-                free_problem(ctx);
-                return fail(ctx, PDH_EDEVICE, "row kernel: hipMemset of the work counter failed");
-              }
-            R.sched = static_cast<unsigned int *>(dq);
-          }
-          {
-            void *ds = nullptr;
-            const size_t nb = (size_t)std::max(K.n_owned, 1) * 16 * sizeof(long long);
-            if (hipMalloc(&ds, nb) == hipSuccess)
-              {
-                ctx->allocs.push_back(ds);
-                (void)hipMemset(ds, 0, nb);
-                R.stamps = static_cast<long long *>(ds);
-              }
-            else
-              R.stamps = nullptr;
-          }
-          R.m2c_scratch = nullptr;
-          R.scratch_waves = 0;
-          R.scratch_stride = 0;
-          if (RH.multi)
-            {
-              // MULTI instantiation: the coupling moments of a polytope's interior entries (8 x 8 doubles each, up to 40 of
-              // them) are parked between P2 and P5 in a per-wave row of this buffer instead of LDS (pdh_rows.h) - 8 waves per
-              // CU at most (256 VGPRs), a few tens of MB that stay in L2 / the memory-side cache
-              int cus = 256;
-              (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-              const int waves = cus * 8;
-              void *dm = nullptr;
-              // (with tensor sub-face rules the row holds 16 + 16 factors per interior sub-face instead, pdh_rows.h: FACT)
-              const size_t stride = std::max<size_t>((size_t)RH.maxf * 64, (size_t)RH.maxs * 32 + 64);
-              R.scratch_stride = (int64_t)stride;
-              if (hipMalloc(&dm, (size_t)waves * stride * sizeof(double)) != hipSuccess)
-                {
-                  free_problem(ctx);
-                  return fail(ctx, PDH_EDEVICE, "row kernel: out of device memory");
-                }
-              ctx->allocs.push_back(dm);
-              R.m2c_scratch = static_cast<double *>(dm);
-              R.scratch_waves = waves;
-            }
-          lap("row kernel: upload");
-          int vq_n = 0;
-          bool tensor_only = false;
-          const bool ok = rows_kind_applies(p, K, RH, vq_n, tensor_only);
-          R.tensor_only = tensor_only ? 1 : 0;
-          R.multi = RH.multi ? 1 : 0;
-          R.maxe = RH.maxe;
-          R.maxf = RH.maxf;
-          R.vq_tensor_n = vq_n;
-          R.fq_tensor_n = RH.fq_tensor_n;
-          ctx->rows_ok = ok;
-          ctx->rows_auto = true;
-          vq_n_terms = vq_n;
-          lap("row kernel: volume rule check");
-        }
-      // term kernel (pdh_terms.h): the small elements on agglomerates of Cartesian cells with tensor rules, any number of planes
-      // per neighbour.  PDH_TERMS=0 (diagnostics) keeps the kinds of pdh_rows.h.
-      const char *terms_e = getenv("PDH_TERMS"); // (read per call: the tests compare both kernels in one process)
-      const bool terms_env = !(terms_e && terms_e[0] == '0');
-      // (FE_DGQ(3) has the workgroup-per-polytope form of the term kernel, pdh_terms_wg.h: the default where it applies since the records
-      // of 1-D rules and the merged cells - 1.28-1.35 ms on the bench mesh where pdh_rows.h takes 1.59-1.66, never slower on the other
-      // shapes tried, profiles/r04_wg_forms.txt; PDH_TERMS_DGQ3=0 keeps pdh_rows.h for that element)
-      const int terms_kind = pdh_terms_has_kind(K.n1d, p->basis == PDH_BASIS_AGGLODGP ? 1 : 0);
-      const char *terms_q3 = getenv("PDH_TERMS_DGQ3");
-      if ((terms_env || cart) && RH.planar_ok && RH.fq_tensor_n > 0 &&
-          (terms_kind == 1 || (terms_kind == 2 && (cart || !(terms_q3 && terms_q3[0] == '0')))))
-        {
-          if (vq_n_terms < 0)
-            vq_n_terms = resolve_tensor_hint(p->vq_tensor_n, [&](int n) { return volume_rules_are_tensor(p, K, n); });
-          TermsHost TH;
-          if (vq_n_terms > 0 && build_terms_tables(p, K, RH, vq_n_terms, TH))
-            {
-              lap("term kernel: tables (host)");
-              PdhTerms &T = ctx->terms;
-              if ((rc = upload(ctx, TH.meta, &T.meta)) != PDH_OK || (rc = upload(ctx, TH.sf_pt, &T.sf_pt)) != PDH_OK ||
-                  (rc = upload(ctx, TH.sf_info, &T.sf_info)) != PDH_OK || (rc = upload(ctx, TH.sf_ivl, &T.sf_ivl)) != PDH_OK ||
-                  (rc = upload(ctx, TH.cell_ivl, &T.cell_ivl)) != PDH_OK)
-                {
-                  free_problem(ctx);
-                  return rc;
-                }
-              lap("term kernel: upload");
-              T.maxruns = TH.maxruns, T.maxsf = TH.maxsf, T.maxsi = TH.maxsi, T.maxcell = TH.maxcell;
-              T.vq_tensor_n = vq_n_terms, T.fq_tensor_n = RH.fq_tensor_n;
-              T.lds_bytes = TH.lds_bytes;
-              T.split = TH.split;
-              T.task_pts = TH.task_pts;
-              {
-                // the 1-D rules the kernels read, gathered on the device from the point arrays (zero-filled: slots behind a rule)
-                T.tpm = TH.task_pts > 4 ? 8 : 4;
-                T.tstride = pdh_terms_task_doubles(T.maxsf, T.maxcell, T.tpm);
-                void *dt = nullptr;
-                const size_t nb = (size_t)std::max(K.n_owned, 1) * T.tstride * sizeof(double);
-                hipError_t eg = hipMalloc(&dt, nb);
-                if (eg == hipSuccess)
-                  {
-                    ctx->allocs.push_back(dt);
-                    eg = hipMemsetAsync(dt, 0, nb, ctx->stream);
-                  }
-                if (eg == hipSuccess)
-                  {
-                    T.tdata = static_cast<const double *>(dt);
-                    eg = pdh_launch_terms_gather(&ctx->dev, &T, static_cast<double *>(dt), K.n_owned, ctx->stream);
-                  }
-                if (eg == hipSuccess)
-                  eg = hipStreamSynchronize(ctx->stream);
-                if (eg != hipSuccess)
-                  {
-                    free_problem(ctx);
-                    return fail(ctx, PDH_EDEVICE, std::string("term kernel: records of 1-D rules: ") + hipGetErrorString(eg));
-                  }
-              }
-              ctx->terms_merge[0] = TH.n_cells_in, ctx->terms_merge[1] = TH.n_cells_out;
-              ctx->terms_merge[2] = TH.n_sf_in, ctx->terms_merge[3] = TH.n_sf_out;
-              {
-                void *ds = nullptr;
-                const size_t nb = (size_t)std::max(K.n_owned, 1) * 16 * sizeof(long long);
-                T.stamps = nullptr;
-                if (hipMalloc(&ds, nb) == hipSuccess)
-                  {
-                    ctx->allocs.push_back(ds);
-                    (void)hipMemset(ds, 0, nb);
-                    T.stamps = static_cast<long long *>(ds);
-                  }
-              }
-              ctx->terms_ok = true;
-              ctx->rows_auto = true;
-              lap("term kernel: records of 1-D rules (device)");
-            }
-        }
-    }
-  if (cart && !ctx->terms_ok)
-    {
-      free_problem(ctx);
-      return fail(ctx, PDH_EUNSUPPORTED, "cartesian description: the term kernels do not apply (a polytope's tables exceed their LDS budget, "
-                                         "or the element has none): describe the problem with its points (pdh_set_problem)");
-    }
+  ctx->row_kernel = plan->kernel;
   ctx->has_problem = true;
   ctx->ev_used = 0;
+  guard.done = true;
   K_owner.reset();
+  plan.reset();
   lap("release host staging");
   return PDH_OK;
 }
@@ -2742,7 +2705,7 @@ extern "C" int pdh_rows_kernel_in_use(pdh_ctx *ctx)
     return fail(ctx, PDH_ESTATE, "no problem resident");
   if (!ctx->use_rows())
     return PDH_ROWS_NONE;
-  if (ctx->terms_ok)
+  if (ctx->row_kernel == RowKernel::terms)
     return PDH_ROWS_TERMS;
   if (ctx->rows.multi)
     return PDH_ROWS_MULTI;
@@ -2767,7 +2730,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
   const int dim = ctx->dev.dim, n1d = ctx->dev.n1d, nt = ctx->NT, lb = ctx->LB;
   if (ctx->algorithm == PDH_ALG_MOMENT && !ctx->d_mtab)
     return fail(ctx, PDH_EUNSUPPORTED, "the moment form exists for 3-D bases of degree 1..3 only");
-  if (ctx->algorithm == PDH_ALG_ROWS && !ctx->use_rows())
+  if (ctx->algorithm == PDH_ALG_ROWS && ctx->row_kernel == RowKernel::none)
     return fail(ctx, PDH_EUNSUPPORTED, "the row kernel does not apply to the resident problem (3-D FE_DGQ / FE_AggloDGP of degree 1 .. 3 on polytopes whose faces are unions of axis-aligned planes, no exchange variant; pdh_check_rows says why)");
   if (ctx->use_rows())
     { // one launch writes everything; reported as kernel 0, kernel 1 takes no time
@@ -2782,7 +2745,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
             return fail(ctx, PDH_EDEVICE, "hipEventCreate failed");
           PDH_HIP(ctx, hipEventRecord(r0, ctx->stream));
         }
-      if (ctx->terms_ok)
+      if (ctx->row_kernel == RowKernel::terms)
         PDH_HIP(ctx, pdh_launch_terms(&ctx->dev, &ctx->terms, ctx->n_owned, ctx->stream));
       else
         PDH_HIP(ctx, pdh_launch_rows(&ctx->dev, &ctx->rows, ctx->d_mtab, ctx->n_owned, ctx->stream));
@@ -2971,7 +2934,10 @@ extern "C" int pdh_set_stream(pdh_ctx *ctx, void *stream)
 // Diagnostic (builds with -DPDHR_STAMP only): s_memtime stamps of the row kernel's phase boundaries and in-phase sums, [n_owned][16].
 extern "C" int pdh_debug_rows_stamps(pdh_ctx *ctx, long long *out)
 {
-  const long long *src = !ctx || !ctx->has_problem ? nullptr : (ctx->terms_ok ? ctx->terms.stamps : (ctx->rows_ok ? ctx->rows.stamps : nullptr));
+  const long long *src = !ctx || !ctx->has_problem ? nullptr
+                         : ctx->row_kernel == RowKernel::terms ? ctx->terms.stamps
+                         : ctx->row_kernel == RowKernel::rows ? ctx->rows.stamps
+                                                                : nullptr;
   if (!src || !out)
     return fail(ctx, PDH_ESTATE, "no row-kernel problem resident");
   PDH_HIP(ctx, hipSetDevice(ctx->device));
@@ -3087,10 +3053,8 @@ static int ensure_ap_src(pdh_ctx *ctx)
         else
           b = std::min(b, fr.ap_begin), e = std::max(e, fr.ap_begin + fr.count); // (several runs: their hull; interior points in between carry no datum)
       }
-  int rc = upload(ctx, bd, &ctx->d_bd_rng);
-  if (rc != PDH_OK)
-    return rc;
-  return upload(ctx, ap_src, &ctx->d_ap_src);
+  PDH_TRY(upload(ctx, bd, &ctx->d_bd_rng, "boundary ranges of the right-hand side"));
+  return upload(ctx, ap_src, &ctx->d_ap_src, "caller face points of the right-hand side");
 }
 
 extern "C" int pdh_assemble_rhs_device(pdh_ctx *ctx, const double *d_f_vol, const double *d_g_bdry, double *d_rhs)

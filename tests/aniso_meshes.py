@@ -49,6 +49,15 @@ def _pinwheel_groups(grid):
     return groups
 
 
+# |x| / h of the origin of "offset_mod" moved to (off, off, off) (cells of 0.25): where the term kernels stop being taken (1 / 0), and
+# whether pdh_rows.h still takes FE_DGQ(3) / FE_AggloDGP(3) (offset_handler, tests/test_anisotropic_cpu.py)
+OFFSET_BOUNDARY = [
+    (0.0, 1, 1), (16.0, 1, 1), (100.0, 1, 1), (300.0, 1, 1),  # |x| / h <= 1204: term kernels
+    (400.0, 0, 1), (1000.0, 0, 1),                            # |x| / h ~ 1600, 4000: rules not tensor to the bound; pdh_rows.h stays
+    (4000.0, 0, 0), (1.0e4, 0, 0),                            # |x| / h ~ 1.6e4, 4e4: not even the normals are axis-aligned to the bound
+]
+
+
 def oracle_grid(name, scale=1.0, shift=None, perm=None):
     """The mesh in the oracle.  scale / shift: x -> scale * x + shift (applied to lo / hi, so the mesh is generated there, not
     mapped); perm: axis permutation - axis c of the new mesh is axis perm[c] of the named one."""
@@ -82,6 +91,28 @@ def oracle_handler(name, fe, nq, groups=None, **grid_kw):
     ah.initialize_fe_values(nq, nq)
     ah.distribute_agglomerated_dofs(fe)
     return ah
+
+
+def offset_handler(off, fe, nq):
+    """"offset_mod" with its lower corner at (off, off, off) (OFFSET_BOUNDARY)."""
+    return oracle_handler("offset_mod", fe, nq, shift=np.full(3, off) - np.array(MESHES["offset_mod"][2]))
+
+
+def kernel_selection(kw):
+    """(pdh_check_terms, its pdh_last_error, pdh_check_rows, its pdh_last_error) of a flattened description: which row kernel the
+    host selection grants (the library's planner, without the diagnostic switches PDH_TERMS / PDH_TERMS_DGQ3)."""
+    import ctypes as C
+
+    import polydeal_amd as pa
+
+    lib = pa.load_library()
+    lib.pdh_last_error.restype = C.c_char_p
+    prob = pa.Problem(**kw)
+    rt = lib.pdh_check_terms(C.byref(prob.c), 0, kw["n_rows"], None)
+    wt = (lib.pdh_last_error(None) or b"").decode()
+    rr = lib.pdh_check_rows(C.byref(prob.c), 0, kw["n_rows"])
+    wr = (lib.pdh_last_error(None) or b"").decode()
+    return rt, wt, rr, wr
 
 
 def mirror_grid(name):

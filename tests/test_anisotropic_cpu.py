@@ -7,8 +7,6 @@ Identities (Nitsche boundary terms, continuous v: the jump terms vanish):
     v = x_c : v^T A v = |Omega| - 2 int_dOmega x_c n_c + sum_P sigma_P int_(dP n dOmega) x_c^2
                       = -|Omega| + sum_P sigma_P int_(dP n dOmega) x_c^2      (int x_c n_c = |Omega|, whatever the origin)
 for EVERY axis c: on a box mesh with h_0 != h_1 != h_2 a swapped axis factor changes the x_c forms."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -89,19 +87,6 @@ def test_oracle_axis_permutation(mesh, p):
 # ---------------------------------------------------------------------------------------------------------------------
 # Which kernel the host selection grants (pdh_check_terms / pdh_check_rows - what AUTO takes for 3-D degree 1 .. 3)
 # ---------------------------------------------------------------------------------------------------------------------
-def _selection(kw):
-    import polydeal_amd as pa
-
-    lib = pa.load_library()
-    lib.pdh_last_error.restype = C.c_char_p
-    prob = pa.Problem(**kw)
-    rt = lib.pdh_check_terms(C.byref(prob.c), 0, kw["n_rows"], None)
-    wt = (lib.pdh_last_error(None) or b"").decode()
-    rr = lib.pdh_check_rows(C.byref(prob.c), 0, kw["n_rows"])
-    wr = (lib.pdh_last_error(None) or b"").decode()
-    return rt, wt, rr, wr
-
-
 @pytest.mark.parametrize("basis,p", ELEMENTS)
 @pytest.mark.parametrize("mesh", ["rect124", "rect1116", "graded", "pinwheel", "offset_mod", "offset_far", "rect2d", "offset2d"])
 def test_kernel_selection_on_box_meshes(mesh, basis, p):
@@ -112,7 +97,7 @@ def test_kernel_selection_on_box_meshes(mesh, basis, p):
     dim = am.MESHES[mesh][0]
     fe = _fe(basis, dim, p)
     ah = am.oracle_handler(mesh, fe, p + 1)
-    rt, wt, rr, wr = _selection(flatten(ah, po.variant_poisson_example(fe)))
+    rt, wt, rr, wr = am.kernel_selection(flatten(ah, po.variant_poisson_example(fe)))
     if dim == 2:
         assert rt == 0 and rr == 0 and "3-D" in wt and "3-D" in wr, (wt, wr)
     elif mesh == "offset_far":
@@ -124,23 +109,15 @@ def test_kernel_selection_on_box_meshes(mesh, basis, p):
         assert rt == 1 and rr == 1, (wt, wr)
 
 
-# |x| / h of the origin (cells of 0.25): where the term kernels stop being taken, and why
-OFFSET_BOUNDARY = [
-    (0.0, 1, 1), (16.0, 1, 1), (100.0, 1, 1), (300.0, 1, 1),  # |x| / h <= 1204: term kernels
-    (400.0, 0, 1), (1000.0, 0, 1),                            # |x| / h ~ 1600, 4000: rules not tensor to the bound; pdh_rows.h stays
-    (4000.0, 0, 0), (1.0e4, 0, 0),                            # |x| / h ~ 1.6e4, 4e4: not even the normals are axis-aligned to the bound
-]
-
-
-@pytest.mark.parametrize("off,terms,rows_p3", OFFSET_BOUNDARY)
+@pytest.mark.parametrize("off,terms,rows_p3", am.OFFSET_BOUNDARY)
 def test_offset_boundary_of_the_fast_path(off, terms, rows_p3):
     """The 4^3-cell mesh of 2^3 blocks, cells of 0.25, moved by `off` in every axis: the offset at which AUTO silently leaves the
     term kernels (geometry_rounding, pdh_capi.cpp) is pinned here - between |x| / h = 1200 and 1600 for FE_AggloDGP(3) / FE_DGQ(3)
     (lower elements: not monotone in the offset, e.g. FE_DGQ(2) refused at 1200 and taken at 1600 - rounding of the points decides)."""
     for basis, p in (("dgp", 3), ("dgq", 3)):
         fe = _fe(basis, 3, p)
-        ah = am.oracle_handler("offset_mod", fe, p + 1, shift=np.full(3, off) - np.array([12.0, -14.0, 7.0]))
-        rt, wt, rr, wr = _selection(flatten(ah, po.variant_poisson_example(fe)))
+        ah = am.offset_handler(off, fe, p + 1)
+        rt, wt, rr, wr = am.kernel_selection(flatten(ah, po.variant_poisson_example(fe)))
         assert rt == terms and rr == rows_p3, (off, basis, wt, wr)
         if not rt:
             assert ("points are not" in wt) if off < 4000 else ("axis-aligned" in wt), wt

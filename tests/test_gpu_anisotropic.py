@@ -273,6 +273,36 @@ def test_cartesian_description_on_box_meshes(mesh, basis, p, vname, diag_first):
     assert np.max(np.abs(vals - vpts)) <= 1e-13 * np.max(np.abs(vpts))
 
 
+SELECTION_ELEMENTS = [("dgq", 1), ("dgq", 2), ("dgq", 3), ("dgp", 1), ("dgp", 2), ("dgp", 3)]
+SELECTION_CASES = ([(m, None) for m, spec in am.MESHES.items() if spec[0] == 3] +
+                   [("offset_mod", off) for off, _, _ in am.OFFSET_BOUNDARY])
+
+
+@pytest.mark.parametrize("basis,p", SELECTION_ELEMENTS)
+@pytest.mark.parametrize("mesh,off", SELECTION_CASES)
+def test_host_selection_is_what_set_problem_takes(mesh, off, basis, p, monkeypatch):
+    """pdh_check_terms / pdh_check_rows (host only; what the CPU tests pin) name the row kernel that pdh_set_problem builds and AUTO
+    runs: the term kernels where the first grants them, else pdh_rows.h where the second does, else none."""
+    import polydeal_amd as pa
+
+    for k in ("PDH_TERMS", "PDH_TERMS_DGQ3"):
+        monkeypatch.delenv(k, raising=False)
+    fe = _fe(basis, 3, p)
+    ah = am.oracle_handler(mesh, fe, p + 1) if off is None else am.offset_handler(off, fe, p + 1)
+    kw = flatten(ah, po.variant_poisson_example(fe))
+    rt, wt, rr, wr = am.kernel_selection(kw)
+    want = "terms" if rt == 1 else ("rows" if rr == 1 else "none")
+    ctx = pa.Context(0)
+    try:
+        ctx.set_problem(pa.Problem(**kw))
+        used, kern = ctx.algorithm_in_use(), ctx.rows_kernel_in_use()
+    finally:
+        ctx.close()
+    got = kern if kern in ("terms", "none") else "rows"
+    assert got == want, (kern, wt, wr)
+    assert (used == "rows") == (got != "none"), (used, kern)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Checks that do not trust the oracle
 # ---------------------------------------------------------------------------------------------------------------------

@@ -16,3 +16,16 @@ extern "C" hipError_t pdh_launch_checksum(const double*,int64_t,double*,hipStrea
 extern "C" int pdh_rows_max_faces(void){return 6;}
 extern "C" int pdh_rows_n_dofs(int n1d,int basis){return basis ? n1d*(n1d+1)*(n1d+2)/6 : n1d*n1d*n1d;}
 extern "C" int pdh_moment_table_doubles(int n1d){const int NA=2*n1d-1;return 3*n1d*n1d*(NA+1)+2*n1d+NA*2*n1d+2*n1d*2*n1d;}
+struct PdhTerms;
+extern "C" hipError_t pdh_launch_terms(const PdhDev*,const PdhTerms*,int,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_terms_gather(const PdhDev*,const PdhTerms*,double*,int,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_tiled(int,int,int,const PdhDev*,int,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_eval_err(int,int,const PdhDev*,int,const double*,const int64_t*,const double*,int64_t,const double*,const double*,const double*,double*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_gen_volume(int,const double*,const double*,const double*,const int32_t*,int64_t,double*,int64_t,double*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_gen_faces(int,const double*,const double*,const double*,const int32_t*,const int32_t*,int64_t,double*,double*,double*,hipStream_t){return hipSuccess;}
+extern "C" int pdh_tiled_has_kind(int dim,int n1d,int){return dim == 3 && n1d >= 5 && n1d <= 8;}
+// (as pdh_terms.hip: FE_DGQ(3) has the workgroup kernel, the other elements of degree 1 .. 3 the wave kernel)
+extern "C" int pdh_terms_has_kind(int n1d,int basis){return (n1d < 2 || n1d > 4 || basis < 0 || basis > 1) ? 0 : (n1d == 4 && basis == 0) ? 2 : 1;}
+// (any size that fits the LDS budget: the host tables of the term kernels are built in full)
+extern "C" int pdh_terms_lds_bytes(int,int,int,int,int,int,int,int){return 1024;}
+extern "C" int pdh_terms_task_doubles(int maxsf,int maxcell,int pm){return (2*maxsf+3*maxcell)*3*pm+2*maxsf;}
