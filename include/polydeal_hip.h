@@ -137,7 +137,9 @@ int pdh_set_problem_local(pdh_ctx *ctx, const pdh_problem *problem, int32_t row_
  *   points  : where the points come from.  Volume group g (the g-th group of nq^3 points in the order of vq_ptr) is QGauss<3>(nq)
  *             on cell vq_cell[g] (x fastest); face group s (order of fq_ptr) is QGauss<2>(nqf) on local face fq_face[s] (deal.II
  *             numbering 2 * axis + side) of cell fq_cell[s] - the sub-cell on side 0 of the polytopal face, whose outward normal
- *             is the face's normal (reference include/poly_utils.h:1881) - lower tangential axis fastest.
+ *             is the face's normal (reference include/poly_utils.h:1881) - lower tangential axis fastest.  g_bdry of
+ *             pdh_assemble_rhs is sampled as for the equivalent points description: QProjector's order, tangential axes
+ *             (y, z), (z, x), (x, y) for faces of axis 0, 1, 2, the first fastest.
  * The generated arrays are exactly what the caller would have passed (to rounding of lo + h * xi), so everything downstream is
  * unchanged; the assembly runs through the term kernels (PDH_ROWS_TERMS: a problem whose polytopes are too large for them is
  * refused with PDH_EUNSUPPORTED - describe it with points then).                                                              */

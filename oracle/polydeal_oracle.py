@@ -889,22 +889,30 @@ def assemble_csr(ah: AgglomerationHandler, var: SipVariant, diag_first: bool = T
     return rowptr, colind, values
 
 
-def assemble_rhs(ah: AgglomerationHandler, var: SipVariant, f=None, g=None):
+def assemble_rhs(ah: AgglomerationHandler, var: SipVariant, f=None, g=None, absolute=False):
     """Right-hand side as the callers assemble it next to the matrix (examples/poisson.cc:745-759, 788-828):
-    volume sum_q phi_i f JxW and Nitsche boundary sum_q (sigma g phi_i - grad phi_i . n g) JxW."""
+    volume sum_q phi_i f JxW and Nitsche boundary sum_q (sigma g phi_i - grad phi_i . n g) JxW.
+    absolute=True: the same loops summing the absolute value of every term instead,
+    sum_q |phi_i f JxW| + sum_q (|sigma g phi_i| + |g grad phi_i . n|) JxW - the scale of entry i that no cancellation
+    shrinks (what a vector's rounding is relative to: tests/parity.py)."""
     b = np.zeros(ah.n_dofs)
+    a = np.abs if absolute else (lambda t: t)
     for P in range(ah.n_agglomerates):
         idx = ah.dof_indices(P)
         if f is not None:
             fv = ah.reinit(P)
-            b[idx] += np.einsum("qi,q->i", fv["val"], f(fv["x"]) * fv["JxW"])
+            b[idx] += np.einsum("qi,q->i", a(fv["val"]), a(f(fv["x"]) * fv["JxW"]))
         if g is not None and var.boundary != "zero":
             for fc in range(ah.n_faces[P]):
                 if ah.at_boundary(P, fc):
                     ff = ah.reinit_face(P, fc)
                     sig = face_sigma(ah, var, P)
                     gn = np.einsum("qic,qc->qi", ff["grad"], ff["normal"])
-                    b[idx] += np.einsum("qi,q->i", sig * ff["val"] - gn, g(ff["x"]) * ff["JxW"])
+                    gw = g(ff["x"]) * ff["JxW"]
+                    if absolute:
+                        b[idx] += np.einsum("qi,q->i", np.abs(sig * ff["val"]) + np.abs(gn), np.abs(gw))
+                    else:
+                        b[idx] += np.einsum("qi,q->i", sig * ff["val"] - gn, gw)
     return b
 
 

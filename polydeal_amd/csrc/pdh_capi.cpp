@@ -167,6 +167,10 @@ struct pdh_ctx
   const int64_t *d_vq_src = nullptr, *d_ap_src = nullptr;
   const int64_t *d_bd_rng = nullptr; // [n_owned][2] packed face points of every slot that lie on the boundary (one run)
   int64_t n_vq_caller = 0, n_fq_caller = 0;
+  // Cartesian description: local face of every sub-face and points per direction (the generated face points run the lower
+  // tangential axis fastest, the caller's g_bdry is in QProjector's order - they differ on faces of axis 1: ensure_ap_src)
+  std::vector<int32_t> cart_fq_face;
+  int cart_nqf = 0;
   // grow-only device scratch for the host-pointer variants of rhs / evaluate / shape_values (no hipMalloc per call)
   struct Scratch { void *p = nullptr; size_t bytes = 0; };
   Scratch scratch[6];
@@ -2486,6 +2490,13 @@ static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
   ctx->vq_src = K.vq_src;
   ctx->n_vq_caller = p->vq_ptr[p->n_agg];
   ctx->n_fq_caller = p->n_faces ? p->fq_ptr[p->n_faces] : 0;
+  ctx->cart_fq_face.clear();
+  ctx->cart_nqf = 0;
+  if (K.cart && K.cart->nqf > 0)
+    {
+      ctx->cart_nqf = K.cart->nqf;
+      ctx->cart_fq_face.assign(K.cart->fq_face, K.cart->fq_face + ctx->n_fq_caller / ((int64_t)K.cart->nqf * K.cart->nqf));
+    }
   ctx->face_runs.clear();
   ctx->face_runs.reserve(K.run_ap.size());
   for (size_t r = 0; r < K.run_ap.size(); ++r)
@@ -3035,11 +3046,21 @@ static int ensure_ap_src(pdh_ctx *ctx)
   if (ctx->d_ap_src)
     return PDH_OK;
   std::vector<int64_t> ap_src((size_t)std::max<int64_t>(ctx->n_ap, 1), -1);
+  // Cartesian description: the packed points are the generated ones (pdh_cartgen.hip: lower tangential axis fastest); the caller
+  // samples g_bdry at the points of the equivalent points description, QProjector's order (y, z), (z, x), (x, y) - on the faces of
+  // axis 1 the two tangential indices are swapped
+  const int64_t nqf = ctx->cart_nqf, m2 = nqf * nqf;
+  auto caller = [&](int64_t q) {
+    if (!nqf || (ctx->cart_fq_face[(size_t)(q / m2)] >> 1) != 1)
+      return q;
+    const int64_t l = q % m2;
+    return q - l + (l / nqf) + nqf * (l % nqf);
+  };
   host_parallel_for(ctx->face_runs.size(), [&](size_t r) {
     const auto &fr = ctx->face_runs[r];
     if (fr.boundary)
       for (int32_t t = 0; t < fr.count; ++t)
-        ap_src[fr.ap_begin + t] = fr.fq_begin + t;
+        ap_src[fr.ap_begin + t] = caller(fr.fq_begin + t);
   });
   // the boundary points of a slot are one contiguous run (all boundary sub-faces form ONE polytopal face, reference
   // source/agglomeration_handler.cc:1575-1613): the kernel visits only that range

@@ -12,7 +12,7 @@ import pytest
 import aniso_meshes as am
 from flatten_oracle import flatten
 from oracle import polydeal_oracle as po
-from parity import assert_parity, assert_parity_ah
+from parity import assert_parity, assert_parity_ah, assert_vector_parity, dof_segments, oracle_evaluate, point_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -205,6 +205,8 @@ def _check_rhs(ah, var, kw):
     got = ctx.assemble_rhs(f(kw["vq_x"].T), g(kw["fq_x"].T))
     ctx.close()
     assert np.max(np.abs(got - ref)) <= 1e-12 * np.max(np.abs(ref))
+    assert_vector_parity(got, ref, dof_segments(ah.n_dofs, ah.fe.n_dofs_per_cell), po.assemble_rhs(ah, var, f, g, absolute=True),
+                         what="rhs")
 
 
 @pytest.mark.parametrize("mesh,basis,p", [("rect124", "dgq", 3), ("graded", "dgp", 2), ("pinwheel", "dgq", 2), ("rect1116", "dgp", 3),
@@ -237,6 +239,10 @@ def test_rhs_evaluate_and_global_error_on_box_meshes(mesh, basis, p):
     assert np.max(np.abs(uh - ref_u)) <= 1e-12 * np.max(np.abs(ref_u))
     for c in range(dim):  # per axis: the gradients differ in size by the aspect ratio
         assert np.max(np.abs(gh[c] - ref_g[c])) <= 1e-12 * np.max(np.abs(ref_g[c])), c
+    ev = [oracle_evaluate(ah, u, P, ah.reinit(P)["x"]) for P in range(ah.n_agglomerates)]
+    seg = point_segments(kw["vq_ptr"])
+    assert_vector_parity(uh, ref_u, seg, np.concatenate([e[2] for e in ev]), what="u_h")
+    assert_vector_parity(gh.T, ref_g.T, seg, np.concatenate([e[3] for e in ev]), what="grad u_h")
     rl2, rh1 = po.compute_global_error(ah, u, exact, exact_grad)
     assert abs(l2 - rl2) <= 1e-12 * rl2 and abs(h1 - rh1) <= 1e-12 * rh1
 

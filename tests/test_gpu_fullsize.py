@@ -440,3 +440,141 @@ def test_config3_anisotropic_box_fullsize():
     sample = np.unique(np.linspace(0, ah.n_dofs - 1, 400).astype(np.int64))
     S = A[sample][:, sample]
     assert abs(S - S.T).max() <= 1e-12 * scale
+
+
+def _abs_1d(nodes, t, vals):
+    """sum_k |vals_k l_k(t)| and sum_k |vals_k l_k'(t)| of the 1-D Lagrange basis on `nodes` at the unit points t (vals [k] or [k][t])"""
+    from oracle.polydeal_oracle import lagrange_1d  # 1-D Lagrange values only (test infrastructure)
+
+    v, d = lagrange_1d(nodes, t)
+    vals = vals[:, None] if vals.ndim == 1 else vals
+    return np.abs(vals * v).sum(axis=0), np.abs(vals * d).sum(axis=0)
+
+
+def test_headline_rhs_evaluate_error_and_checksum_fullsize():
+    """rhs, u_h, the error sums and the checksum at the headline size (64^3 cells, 32768 polytopes, FE_DGQ(3)), through both the points
+    description and the Cartesian one.  No oracle: FE_DGQ is a partition of unity and reproduces polynomials of degree <= 3 per axis, so
+      sum_{i in P} rhs_i = sum_{q in P} f w + sum_{boundary faces F of P} sigma_F sum_{q in F} g w       (per polytope)
+      v_x^T rhs          = sum_q x_0 f w + sum_{boundary q} (sigma x_0 - n_0) g w
+      u_h                = q(x), grad u_h = grad q(x) at every volume point (coefficients: nodal values of q)
+      error sums         = (|Omega|, 0) for exact = q + 1;   checksum sum = 1^T A 1 = sigma |dOmega|.
+    Each to 1e-12 of a scale that cancellation cannot shrink: the sum of the absolute terms, formed exactly from the 1-D factors (the sum
+    over a tensor product of |products| is the product of the 1-D sums)."""
+    from oracle.polydeal_oracle import gauss_lobatto_nodes
+
+    fe = pa.FE_DGQ(3, 3)
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, 6)
+    ah = pa.AgglomerationHandler(grid)
+    ah.define_block_agglomerates(2)
+    ah.initialize_fe_values(4, 4)
+    ah.distribute_agglomerated_dofs(fe)
+    var = pa.SipVariant.poisson_example(fe)
+    n, nA, p = fe.n_dofs_per_cell, ah.n_agglomerates, fe.degree
+    assert nA == 32768
+    pf = ah.flatten(var, True, False)
+    arr = pf.arrays()
+    vq_ptr, vw = arr["vq_ptr"], arr["vq_w"]
+    vx = arr["vq_x"].reshape(3, -1)
+    N = len(vw)
+    fp, fo, fi, sig = arr["fq_ptr"], arr["face_out"], arr["face_in"], arr["face_sigma"]
+    fx, fn, fw = arr["fq_x"].reshape(3, -1), arr["fq_n"].reshape(3, -1), arr["fq_w"]
+    fseg = np.repeat(np.arange(len(fo)), np.diff(fp))
+    bpt = fo[fseg] < 0
+    bq = np.nonzero(bpt)[0]
+    bpoly, bsig = fi[fseg[bq]], sig[fseg[bq]]
+    f = np.sin(2.0 * vx[0]) + vx[1] ** 2 + vx[2]
+    g = np.where(bpt, 1.0 + fx[0] * fx[1] - 0.5 * fx[2], 0.0)
+    blo, bhi = arr["bbox"].reshape(nA, 2, 3)[:, 0], arr["bbox"].reshape(nA, 2, 3)[:, 1]
+    vseg = np.repeat(np.arange(nA), np.diff(vq_ptr))
+    nodes = gauss_lobatto_nodes(p)
+    ones = np.ones(p + 1)
+    # per-point sums of |phi_i| (L) and of |grad phi_i . n| (D, boundary points)
+    L = np.ones(N)
+    for c in range(3):
+        L *= _abs_1d(nodes, (vx[c] - blo[vseg, c]) / (bhi[vseg, c] - blo[vseg, c]), ones)[0]
+    bx = fx[:, bq]
+    Lb, D = np.ones(len(bq)), np.zeros(len(bq))
+    vb, db = [], []
+    for c in range(3):
+        h = bhi[bpoly, c] - blo[bpoly, c]
+        v_, d_ = _abs_1d(nodes, (bx[c] - blo[bpoly, c]) / h, ones)
+        vb.append(v_)
+        db.append(d_ / h)
+        Lb *= v_
+    for c in range(3):
+        D += np.abs(fn[c, bq]) * db[c] * vb[(c + 1) % 3] * vb[(c + 2) % 3]
+    S = np.add.reduceat(L * np.abs(f) * vw, vq_ptr[:-1])
+    np.add.at(S, bpoly, (bsig * Lb + D) * np.abs(g[bq]) * fw[bq])
+    ref = np.add.reduceat(f * vw, vq_ptr[:-1])
+    np.add.at(ref, bpoly, bsig * g[bq] * fw[bq])
+    _, vxc, off = coefficient_vectors(ah, fe)
+    x0_closed = math.fsum(vx[0] * f * vw) + math.fsum((bsig * fx[0, bq] - fn[0, bq]) * g[bq] * fw[bq])
+    x0_scale = math.fsum(np.max(np.abs(vxc[off[:, None] + np.arange(n)[None, :]]), axis=1) * S)
+    # u_h of q(x) = (1 + x0 - 2 x0^2 + x0^3 / 2)(1/2 - x1 + x1^3)(2 + x2^2), and of x_0: nodal coefficients, exact values, exact scales
+    digit = [(np.arange(n) // (p + 1) ** c) % (p + 1) for c in range(3)]
+    idx = off[:, None] + np.arange(n)[None, :]  # dofs of every polytope
+
+    def separable(qs, dqs):
+        """coefficients, values, gradients and the scales sum_i |c_i phi_i|, sum_i |c_i d_c phi_i| at the volume points"""
+        coef = np.ones((nA, n))
+        val, grad, sc, gsc = np.ones(N), np.ones((3, N)), np.ones(N), np.ones((3, N))
+        for c in range(3):
+            coef *= qs[c](blo[:, c:c + 1] + nodes[digit[c]][None, :] * (bhi - blo)[:, c:c + 1])
+            h = bhi[vseg, c] - blo[vseg, c]
+            qv, qd = qs[c](vx[c]), dqs[c](vx[c])
+            sv, sd = _abs_1d(nodes, (vx[c] - blo[vseg, c]) / h, qs[c](blo[vseg, c][None, :] + nodes[:, None] * h[None, :]))
+            val *= qv
+            sc *= sv
+            for g_ in range(3):
+                grad[g_] *= qd if g_ == c else qv
+                gsc[g_] *= sd / h if g_ == c else sv
+        cv = np.zeros(ah.n_dofs)
+        cv[idx] = coef
+        return cv, val, grad, sc, gsc
+
+    one, zero = (lambda t: np.ones_like(t)), (lambda t: np.zeros_like(t))
+    polys = [separable([lambda t: t, one, one], [one, zero, zero]),
+             separable([lambda t: 1 + t - 2 * t * t + 0.5 * t ** 3, lambda t: 0.5 - t + t ** 3, lambda t: 2 + t * t],
+                       [lambda t: 1 - 4 * t + 1.5 * t * t, lambda t: -1 + 3 * t * t, lambda t: 2 * t])]
+    assert np.array_equal(polys[0][0], vxc)
+    del L
+    sigma = var.penalty_constant / ah.diameter(0)
+    cf = ah.flatten_cartesian(var, True, False)
+    assert cf.cartesian and not pf.cartesian
+    for name, view in (("points", pf), ("cartesian", cf)):
+        ctx = pa.Context(0)
+        try:
+            ctx.set_problem(view)
+            assert ctx.algorithm_in_use() == "rows" and ctx.rows_kernel_in_use() == "terms", name
+            rhs = ctx.assemble_rhs(f, g)
+            got = rhs[idx].sum(axis=1)
+            ratio = np.abs(got - ref) / (1e-12 * S)
+            assert ratio.max() <= 1.0, (name, float(ratio.max()), int(np.argmax(ratio)))
+            xm = math.fsum(vxc * rhs)
+            assert abs(xm - x0_closed) <= 1e-12 * x0_scale, (name, xm, x0_closed)
+            del rhs
+            for k, (coef, val, grad, sc, gsc) in enumerate(polys):
+                u, gr = ctx.evaluate(coef, vq_ptr, vx, want_grad=True)
+                r = np.abs(u - val) / (1e-12 * sc)
+                assert r.max() <= 1.0, (name, k, float(r.max()))
+                for c in range(3):
+                    r = np.abs(gr[c] - grad[c]) / (1e-12 * gsc[c])
+                    assert r.max() <= 1.0, (name, k, c, float(r.max()))
+                del u, gr
+                l2, h1 = ctx.global_error_sums(coef, vq_ptr, vx, vw, val + 1.0, grad)
+                assert abs(l2 - 1.0) <= 1e-12 and abs(h1) <= 1e-12, (name, k, l2, h1)
+            ctx.assemble_device()
+            ctx.synchronize()
+            cs = ctx.checksum()
+            vals = ctx.values()
+            ch = [np.sum(vals[k:k + (1 << 20)]) for k in range(0, len(vals), 1 << 20)]
+            ach = [np.sum(np.abs(vals[k:k + (1 << 20)])) for k in range(0, len(vals), 1 << 20)]
+            s_ref, a_ref = math.fsum(ch), math.fsum(ach)
+            assert cs["non_finite"] == 0 and cs["max_abs"] == float(np.max(np.abs(vals)))
+            del vals
+            assert abs(cs["sum"] - s_ref) <= 1e-13 * a_ref and abs(cs["abs_sum"] - a_ref) <= 1e-13 * a_ref, (name, cs, s_ref, a_ref)
+            closed = math.fsum(sig[fo < 0] * np.add.reduceat(fw, fp[:-1])[fo < 0])
+            assert abs(closed - 6.0 * sigma) <= 1e-12 * 6.0 * sigma
+            assert abs(cs["sum"] - closed) <= 1e-13 * cs["abs_sum"], (name, cs["sum"], closed)
+        finally:
+            ctx.close()

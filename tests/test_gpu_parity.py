@@ -7,7 +7,7 @@ import pytest
 import golden_cases as gc
 from flatten_oracle import flatten
 from oracle import polydeal_oracle as po
-from parity import assert_parity, assert_parity_ah
+from parity import assert_parity, assert_parity_ah, assert_vector_parity, dof_segments, oracle_evaluate, point_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -87,6 +87,7 @@ TILED_CASES = [
     (1, 1, po.FE_AggloDGP, 7, "dr", 0.0, False),     # n = 120, N1D = 8
     (1, 1, po.FE_DGQ, 5, "poisson", 0.1, True),      # n = 216: 4 x 4 tiles, the last one 24 wide
     (1, 1, po.FE_DGQ, 6, "adm", 0.1, True),          # n = 343: the largest degree examples/3D_piston.cc:912-914 runs
+    (1, 1, po.FE_DGQ, 7, "poisson", 0.0, True),      # n = 512, N1D = 8: 8 x 8 tiles, the largest element instantiated
 ]
 
 
@@ -116,6 +117,8 @@ def test_more_than_64_dofs_per_polytope(case):
     got_rhs = ctx.assemble_rhs(f(kw["vq_x"].T), g(kw["fq_x"].T))
     ctx.close()
     assert np.max(np.abs(got_rhs - ref_rhs)) <= 1e-12 * np.max(np.abs(ref_rhs))
+    assert_vector_parity(got_rhs, ref_rhs, dof_segments(ah.n_dofs, fe.n_dofs_per_cell), po.assemble_rhs(ah, var, f, g, absolute=True),
+                         what="rhs")
 
 
 def test_irregular_agglomerates_and_ascending_layout():
@@ -349,6 +352,9 @@ def test_rhs_parity(dim, lg, b, fe_cls, p, dist):
     ref_f = po.assemble_rhs(ah, var, f, None)
     assert np.max(np.abs(got - ref)) <= TOL * np.max(np.abs(ref))
     assert np.max(np.abs(got_f - ref_f)) <= TOL * np.max(np.abs(ref_f))
+    seg = dof_segments(ah.n_dofs, fe.n_dofs_per_cell)
+    assert_vector_parity(got, ref, seg, po.assemble_rhs(ah, var, f, g, absolute=True), what="rhs f+g")
+    assert_vector_parity(got_f, ref_f, seg, po.assemble_rhs(ah, var, f, None, absolute=True), what="rhs f")
 
 
 def test_poisson_output_L2_error_all_on_gpu():
@@ -508,6 +514,10 @@ def test_evaluate_and_global_error_parity(dim, lg, b, fe_cls, p, dist):
     assert np.array_equal(uh, uh_only)
     assert np.max(np.abs(uh - ref_u)) <= TOL * np.max(np.abs(ref_u))
     assert np.max(np.abs(gh - ref_g)) <= TOL * np.max(np.abs(ref_g))
+    ev = [oracle_evaluate(ah, u, P, ah.reinit(P)["x"]) for P in range(ah.n_agglomerates)]
+    seg = point_segments(kw["vq_ptr"])
+    assert_vector_parity(uh, ref_u, seg, np.concatenate([e[2] for e in ev]), what="u_h")
+    assert_vector_parity(gh.T, ref_g.T, seg, np.concatenate([e[3] for e in ev]), what="grad u_h")
     rl2, rh1 = po.compute_global_error(ah, u, exact, exact_grad)
     assert abs(l2 - rl2) <= TOL * rl2 and abs(h1 - rh1) <= TOL * rh1
     # the sums are formed on the device (pdh_global_error: 16 bytes per polytope come back): same numbers as summing the
@@ -639,6 +649,9 @@ def test_injection_matrix_parity(dim, lg, bc, bf, p, dist):
     rows = np.repeat(np.arange(len(rp) - 1), n)
     got[rows, ci] = va
     assert np.max(np.abs(got - M)) <= TOL * np.max(np.abs(M))
+    # per (fine polytope, coarse basis function): the values of one function at one box's points
+    ref_v = M[rows, ci].reshape(-1, n)
+    assert_vector_parity(va.reshape(-1, n), ref_v, dof_segments(len(rp) - 1, n), np.abs(ref_v), what="shape values")
     f = lambda x: 1.0 + x[:, 0] ** p - 0.5 * x[:, 1] ** p * x[:, 0] + (x[:, -1] ** p if dim == 3 else 0.0)
     err = got @ po.interpolate_nodal(oracles[0], f) - po.interpolate_nodal(oracles[1], f)
     assert np.max(np.abs(err)) < 5e-13
