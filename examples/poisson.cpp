@@ -7,7 +7,9 @@
 //   output_results :1004-1070  interpolate_to_fine_grid (values at the vertices of the sub-cells) and compute_global_error
 //   run :1090-1106       prints "Time taken by assemble_system(): ... seconds"
 // `poisson --bench [dim refine degree]` keeps the device-resident timing of BASELINE.json configs[1] (2-D, 4096 polytopes).
-// Usage: poisson [path/to/t3.msh]
+// `poisson --device-solve [mesh]` solves on the GPU instead (pdh_setup_preconditioner(BLOCK_JACOBI) + pdh_solve_cg on the resident
+// matrix), after the case of the reference's test/polydeal/poisson.cc, whose printed line "L2 error:0.00647702" it reproduces.
+// Usage: poisson [--device-solve] [path/to/t3.msh]
 #include "../polydeal_amd/csrc/host/polydeal_host.h"
 #include "host_solver.h"
 
@@ -32,12 +34,35 @@ std::string find_mesh(int argc, char **argv)
 }
 
 int bench(int argc, char **argv); // device-resident timing (below)
+int reference_case();             // test/polydeal/poisson.cc, solved on the device (below)
+
+// preconditioned CG on the resident matrix: block Jacobi, the stop rule of example_solver::solve_cg
+int device_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<double> &x)
+{
+  x.assign(rhs.size(), 0.0);
+  const pdh_cg_control control = {20000, 1e-13, 0.0};
+  pdh_cg_result res;
+  if (pdh_setup_preconditioner(ctx, PDH_PREC_BLOCK_JACOBI) != PDH_OK || pdh_solve_cg(ctx, &control, rhs.data(), x.data(), &res) != PDH_OK)
+    {
+      std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
+      return -1;
+    }
+  return res.iterations;
+}
 } // namespace
 
 int main(int argc, char **argv)
 {
   if (argc > 1 && std::strcmp(argv[1], "--bench") == 0)
     return bench(argc - 1, argv + 1);
+  const bool on_device = argc > 1 && std::strcmp(argv[1], "--device-solve") == 0;
+  if (on_device)
+    {
+      --argc;
+      ++argv;
+      if (reference_case() != 0)
+        return 1;
+    }
   constexpr int dim = 2;
   const std::string mesh = find_mesh(argc, argv);
   const double pi = M_PI;
@@ -107,7 +132,9 @@ int main(int argc, char **argv)
 
       // ---- solve()
       std::vector<double> solution;
-      const int its = example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
+      const int its = on_device ? device_solve(ctx, rhs, solution) : example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
+      if (its < 0)
+        return 1;
       std::fprintf(stderr, "  (%u dofs, %d CG iterations)\n", N, its);
 
       // ---- output_results(): interpolate_to_fine_grid = u_h at the vertices of every sub-cell (include/poly_utils.h:1196-1233)
@@ -162,6 +189,89 @@ int main(int argc, char **argv)
 
 namespace
 {
+// test/polydeal/poisson.cc:122-241, 286-303, 492-523: [-1,1]^2 refined 6 times, 7 two-cell agglomerates + singletons, FE_DGQ(1),
+// QGauss(3), penalty 20 / h_f with h_f the master cell's edge, f = 8 pi^2 sin(2 pi x) sin(2 pi y), homogeneous Dirichlet datum; the
+// L2 error of the nodal interpolant onto the sub-cells at their midpoints (QGauss(1)).  Matrix, right-hand side, solve and
+// evaluation on the device.
+int reference_case()
+{
+  const BackgroundGrid tria = BackgroundGrid::hyper_cube_refined(2, -1., 1., 6);
+  AgglomerationHandler ah(tria);
+  const std::vector<std::vector<int>> groups = {{3235, 3238}, {831, 874}, {1226, 1227}, {2278, 2279},
+                                                {3760, 3761}, {3306, 3648}, {3764, 3765}};
+  std::vector<char> grouped((size_t)tria.n_active_cells(), 0);
+  for (const auto &g : groups)
+    {
+      ah.define_agglomerate(g);
+      for (int c : g)
+        grouped[c] = 1;
+    }
+  for (int c = 0; c < tria.n_active_cells(); ++c)
+    if (!grouped[c])
+      ah.define_agglomerate({c});
+  FiniteElement fe;
+  fe.dim = 2;
+  fe.degree = 1;
+  fe.basis = PDH_BASIS_DGQ;
+  ah.initialize_fe_values(3, 3);
+  ah.distribute_agglomerated_dofs(fe);
+  SipVariant var;
+  var.penalty_constant = 20.0 / (2.0 / 64);
+  var.owner_rule = 1;
+  var.h_rule = 1;
+  FlatProblem F;
+  ah.flatten(var, F, false, false);
+  pdh_ctx *ctx = nullptr;
+  const double pi = M_PI;
+  const int64_t nq = F.vq_ptr.back();
+  std::vector<double> f_vol((size_t)nq), rhs(ah.n_dofs()), u;
+  for (int64_t q = 0; q < nq; ++q)
+    f_vol[q] = 8.0 * pi * pi * std::sin(2.0 * pi * F.vq_x[q]) * std::sin(2.0 * pi * F.vq_x[nq + q]);
+  if (pdh_create(&ctx, 0) != PDH_OK || pdh_set_problem(ctx, &F.c) != PDH_OK || pdh_assemble_device(ctx) != PDH_OK ||
+      pdh_assemble_rhs(ctx, f_vol.data(), nullptr, rhs.data()) != PDH_OK)
+    {
+      std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
+      return 1;
+    }
+  const int its = device_solve(ctx, rhs, u);
+  if (its < 0)
+    return 1;
+  std::vector<int64_t> pt_ptr(1, 0);
+  std::vector<double> px, py;
+  for (unsigned P = 0; P < ah.n_agglomerates(); ++P)
+    {
+      for (int cell : ah.get_agglomerate((int)P))
+        for (int v = 0; v < 4; ++v)
+          {
+            px.push_back(tria.vertex(cell, v)[0]);
+            py.push_back(tria.vertex(cell, v)[1]);
+          }
+      pt_ptr.push_back((int64_t)px.size());
+    }
+  const size_t np = px.size();
+  std::vector<double> pts(2 * np), uh(np);
+  std::copy(px.begin(), px.end(), pts.begin());
+  std::copy(py.begin(), py.end(), pts.begin() + np);
+  if (pdh_evaluate(ctx, u.data(), pt_ptr.data(), pts.data(), uh.data(), nullptr) != PDH_OK)
+    {
+      std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
+      return 1;
+    }
+  pdh_destroy(ctx);
+  double err2 = 0.0;
+  for (size_t c = 0; c < np / 4; ++c)
+    {
+      const double *x = &px[4 * c], *y = &py[4 * c];
+      const double mid[2] = {0.25 * (x[0] + x[1] + x[2] + x[3]), 0.25 * (y[0] + y[1] + y[2] + y[3])};
+      const double uh_mid = 0.25 * (uh[4 * c] + uh[4 * c + 1] + uh[4 * c + 2] + uh[4 * c + 3]);
+      const double d = uh_mid - std::sin(2.0 * pi * mid[0]) * std::sin(2.0 * pi * mid[1]);
+      err2 += (x[1] - x[0]) * (y[2] - y[0]) * d * d;
+    }
+  std::fprintf(stderr, "  (reference case: %u dofs, %d CG iterations on the device)\n", ah.n_dofs(), its);
+  std::cout << "L2 error:" << std::sqrt(err2) << std::endl;
+  return 0;
+}
+
 int bench(int argc, char **argv)
 {
   const int dim = argc > 1 ? std::atoi(argv[1]) : 2;

@@ -37,6 +37,7 @@ extern "C" {
 #define PDH_EUNSUPPORTED -2 /* valid but outside what the kernels implement */
 #define PDH_EDEVICE -3    /* HIP runtime error (no GPU, OOM, launch failure) */
 #define PDH_ESTATE -4     /* call order (e.g. assemble before set_problem)  */
+#define PDH_ENOCONV -5    /* iterative solver hit max_iter; x holds the last iterate */
 
 typedef struct pdh_ctx pdh_ctx; /* opaque; owns all device memory */
 
@@ -327,6 +328,48 @@ int pdh_kernel_work(pdh_ctx *ctx, int64_t *mfma_instr /* [PDH_N_KERNELS] */);
 /* Host-only validation of a problem description: runs every check of pdh_set_problem_local without
  * touching a GPU (usable on a build machine).  stats as in pdh_problem_stats, may be NULL.          */
 int pdh_check_problem(const pdh_problem *problem, int32_t row_begin, int32_t row_end, int64_t *stats);
+
+/* Solving with the resident matrix (pdh_solve.hip).  The values are used as they stand in HBM: after pdh_assemble* or
+ * pdh_exchange_apply.  Every call needs a resident problem (else PDH_ESTATE).  Every sum (dot products, norms) is formed in a fixed
+ * order - per-polytope partials, then one fixed-order pass - so the same call on the same data gives the same bits.
+ *
+ * y = A x for the owned rows.  x [n_rows] is in the GLOBAL dof numbering (dof_offset): a rank-local context reads its ghost columns
+ * from it; y [row_end-row_begin] is overwritten.  Every resident problem (global, row range, rank-local, Cartesian, more than 64 dofs
+ * per polytope; both layouts, col_offset included).  x and y must not overlap (PDH_EINVAL).  The _device variant takes device
+ * pointers and is asynchronous on pdh_stream().                                                                                    */
+int pdh_vmult(pdh_ctx *ctx, const double *x, double *y);
+int pdh_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y);
+
+/* Preconditioners, built from the values as they stand (like deal.II's precondition.initialize(A)).  A diagonal block that is not
+ * positive definite (a Cholesky pivot <= 0 or not finite) - for point Jacobi a zero or non-finite diagonal entry - makes the set-up
+ * fail with PDH_EINVAL naming the first such polytope.  PDH_PREC_BLOCK_JACOBI needs n <= 64 dofs per polytope (PDH_EUNSUPPORTED).
+ * pdh_precondition_device (z = P^-1 r over the owned rows, device pointers, asynchronous) and pdh_solve_cg* return PDH_ESTATE when
+ * the values changed (pdh_set_problem*, pdh_assemble*, pdh_exchange_apply) since the set-up.  PDH_PREC_NONE needs no set-up call. */
+#define PDH_PREC_NONE 0
+#define PDH_PREC_JACOBI 1       /* inverse of the diagonal                                */
+#define PDH_PREC_BLOCK_JACOBI 2 /* inverses of the n x n diagonal blocks, one per polytope */
+int pdh_setup_preconditioner(pdh_ctx *ctx, int kind);
+int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *d_z);
+
+/* Conjugate gradients preconditioned with the preconditioner set up last (none if there was no set-up).  x: initial guess in,
+ * solution out.  Stops when ||r||_2 <= max(abs_tol, rel_tol * ||b||_2), tested before every iteration.  Needs a context that owns
+ * ALL rows with PDH_EXCHANGE_NONE (else PDH_EUNSUPPORTED).  At max_iter it returns PDH_ENOCONV with res and x filled.  b and x must
+ * not overlap.  The _device variant takes device pointers and synchronises before it returns.  Scratch vectors and the inverse
+ * blocks are grow-only buffers of the context, allocated at first use, freed with the problem.                                     */
+typedef struct pdh_cg_control
+{
+  int32_t max_iter;
+  double rel_tol;
+  double abs_tol;
+} pdh_cg_control;
+typedef struct pdh_cg_result
+{
+  int32_t iterations;
+  double residual0; /* ||b - A x0||_2 */
+  double residual;  /* ||r||_2 at the end */
+} pdh_cg_result;
+int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *control, const double *b, double *x, pdh_cg_result *result);
+int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *control, const double *d_b, double *d_x, pdh_cg_result *result);
 
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);

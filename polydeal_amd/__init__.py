@@ -5,6 +5,7 @@ operator surface; ``_capi`` ctypes binding of the C ABI; ``handler`` Python face
 There is no CPU compute path: without libpolydeal_hip.so / a HIP device the compute calls raise.
 """
 from ._capi import Context, PdhError, Problem, load_library, PDH_BASIS_AGGLODGP, PDH_BASIS_DGQ  # noqa: F401
+from ._capi import PDH_ENOCONV, PDH_PREC_BLOCK_JACOBI, PDH_PREC_JACOBI, PDH_PREC_NONE  # noqa: F401
 from .handler import (AgglomerationHandler, BackgroundGrid, FE_AggloDGP, FE_DGQ, FiniteElement, HostError,  # noqa: F401
                       SipVariant, assemble_dg_matrix, fill_injection_matrix)
 

@@ -17,13 +17,24 @@ LIB_PATH = os.environ.get("PDH_LIB") or os.path.join(_HERE, "lib", "libpolydeal_
 PDH_BASIS_DGQ = 0
 PDH_BASIS_AGGLODGP = 1
 PDH_OK = 0
-PDH_EINVAL, PDH_EUNSUPPORTED, PDH_EDEVICE, PDH_ESTATE = -1, -2, -3, -4
+PDH_EINVAL, PDH_EUNSUPPORTED, PDH_EDEVICE, PDH_ESTATE, PDH_ENOCONV = -1, -2, -3, -4, -5
+PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI = 0, 1, 2
+_PREC = {"none": PDH_PREC_NONE, "jacobi": PDH_PREC_JACOBI, "block_jacobi": PDH_PREC_BLOCK_JACOBI}
+CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
 
 class PdhError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("pdh error %d: %s" % (code, msg))
         self.code = code
+
+
+class pdh_cg_control(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double)]
+
+
+class pdh_cg_result(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("residual0", C.c_double), ("residual", C.c_double)]
 
 
 class pdh_problem(C.Structure):
@@ -51,6 +62,7 @@ EXPORTS = [
     "pdh_check_exchange", "pdh_copy_values", "pdh_check_rows", "pdh_values_checksum",
     "pdh_assemble_rhs_device", "pdh_evaluate_device", "pdh_shape_values_device",
     "pdh_global_error", "pdh_global_error_device", "pdh_rows_kernel_in_use", "pdh_check_terms", "pdh_terms_merge_stats", "pdh_set_problem_cartesian",
+    "pdh_vmult", "pdh_vmult_device", "pdh_setup_preconditioner", "pdh_precondition_device", "pdh_solve_cg", "pdh_solve_cg_device",
 ]
 
 _lib = None
@@ -121,6 +133,12 @@ def _bind(lib):
     lib.pdh_kernel_work.argtypes = [C.c_void_p, P(C.c_int64)]
     lib.pdh_check_problem.argtypes = [P(pdh_problem), C.c_int32, C.c_int32, P(C.c_int64)]
     lib.pdh_version.restype = C.c_char_p
+    lib.pdh_vmult.argtypes = [C.c_void_p] * 3
+    lib.pdh_vmult_device.argtypes = [C.c_void_p] * 3
+    lib.pdh_setup_preconditioner.argtypes = [C.c_void_p, C.c_int]
+    lib.pdh_precondition_device.argtypes = [C.c_void_p] * 3
+    lib.pdh_solve_cg.argtypes = [C.c_void_p, P(pdh_cg_control), C.c_void_p, C.c_void_p, P(pdh_cg_result)]
+    lib.pdh_solve_cg_device.argtypes = [C.c_void_p, P(pdh_cg_control), C.c_void_p, C.c_void_p, P(pdh_cg_result)]
     return real
 
 
@@ -206,7 +224,9 @@ class Context:
             self._chk(self.lib.pdh_set_problem_cartesian(self.h, C.byref(prob.c), C.c_void_p(cart), row_begin, row_end))
         else:
             self._chk(self.lib.pdh_set_problem_local(self.h, C.byref(prob.c), row_begin, row_end))
-        self.n_values = self.stats()["n_values"]
+        st = self.stats()
+        self.n_values = st["n_values"]
+        self.n_rows, self.n_rows_owned = int(prob.c.n_rows), st["n_owned_agg"] * st["dofs_per_cell"]
         off = np.array((C.c_int32 * prob.c.n_agg).from_address(int(prob.c.dof_offset)), dtype=np.int64)
         self._owned = (off >= row_begin) & (off < row_end)  # polytopes whose rows live here
 
@@ -317,6 +337,58 @@ class Context:
         self.synchronize()
         if hip.hipMemset(C.c_void_p(ptr), 0xFF, C.c_size_t(8 * n)) != 0 or hip.hipDeviceSynchronize() != 0:
             raise PdhError(-1, "hipMemset of the values failed")
+
+    # -- solving with the resident matrix (include/polydeal_hip.h: pdh_vmult, pdh_setup_preconditioner, pdh_solve_cg) ------
+    def vmult(self, x):
+        """A x for the owned rows; x [n_rows] in the global dof numbering."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.shape != (self.n_rows,):
+            raise ValueError("x must have n_rows = %d entries" % self.n_rows)
+        y = np.empty(self.n_rows_owned)
+        self._chk(self.lib.pdh_vmult(self.h, xx.ctypes.data, y.ctypes.data))
+        return y
+
+    def vmult_device(self, d_x, d_y):
+        """Device pointers (ints); asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_vmult_device(self.h, C.c_void_p(d_x), C.c_void_p(d_y)))
+
+    def setup_preconditioner(self, kind):
+        """'none' | 'jacobi' | 'block_jacobi' (or PDH_PREC_*), built from the values as they stand."""
+        self._chk(self.lib.pdh_setup_preconditioner(self.h, _PREC[kind] if isinstance(kind, str) else int(kind)))
+
+    def precondition_device(self, d_r, d_z):
+        self._chk(self.lib.pdh_precondition_device(self.h, C.c_void_p(d_r), C.c_void_p(d_z)))
+
+    def _cg(self, fn, b, x, rel_tol, abs_tol, max_iter, on_noconv):
+        ctl = pdh_cg_control(CG_MAX_ITER if max_iter is None else int(max_iter), float(rel_tol), float(abs_tol))
+        res = pdh_cg_result()
+        rc = fn(self.h, C.byref(ctl), b, x, C.byref(res))
+        info = {"iterations": int(res.iterations), "residual0": float(res.residual0), "residual": float(res.residual)}
+        if rc == PDH_ENOCONV:
+            e = PdhError(rc, self.lib.pdh_last_error(self.h).decode())
+            e.info = info
+            on_noconv(e)
+            raise e
+        self._chk(rc)
+        return info
+
+    def solve_cg(self, b, x0=None, rel_tol=1e-13, abs_tol=0.0, max_iter=None):
+        """Preconditioned CG with the preconditioner set up last; returns (x, info), info = {iterations, residual0, residual}.
+        PDH_ENOCONV raises PdhError carrying .x (the last iterate) and .info."""
+        bb = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros(self.n_rows) if x0 is None else np.array(x0, dtype=np.float64, copy=True)
+        if bb.shape != (self.n_rows,) or x.shape != (self.n_rows,):
+            raise ValueError("b and x0 must have n_rows = %d entries" % self.n_rows)
+
+        def attach(e):
+            e.x = x
+        info = self._cg(self.lib.pdh_solve_cg, C.c_void_p(bb.ctypes.data), C.c_void_p(x.ctypes.data), rel_tol, abs_tol, max_iter, attach)
+        return x, info
+
+    def solve_cg_device(self, d_b, d_x, rel_tol=1e-13, abs_tol=0.0, max_iter=None):
+        """Device pointers (ints); d_x holds the initial guess and receives the solution.  Returns info (PDH_ENOCONV raises
+        PdhError carrying .info; d_x then holds the last iterate)."""
+        return self._cg(self.lib.pdh_solve_cg_device, C.c_void_p(d_b), C.c_void_p(d_x), rel_tol, abs_tol, max_iter, lambda e: None)
 
     def set_algorithm(self, alg):
         """'auto' | 'direct' (MFMA contraction over the points) | 'moment' (Legendre moments + sum factorisation)."""

@@ -8,6 +8,7 @@
 #include "../../include/polydeal_hip.h"
 #include "pdh_basis.h"
 #include "pdh_kernels.h"
+#include "pdh_solve.h"
 
 #include <hip/hip_runtime.h>
 
@@ -190,6 +191,46 @@ struct pdh_ctx
       }
     return s.p;
   }
+  // solving with the resident matrix (pdh_solve.hip): first global dof of every block of every owned slot in value order, the longest
+  // row, the global row count; a generation of the values (bumped by every set_problem / assemble / exchange_apply) against which
+  // the preconditioner is checked; grow-only device buffers of the solver (allocated at first use, freed with the problem) and
+  // the pinned word the CG loop reads its residual through
+  const int64_t *d_blk_ptr = nullptr;
+  const int32_t *d_blk_dof = nullptr;
+  int max_row_len = 0;
+  int64_t n_rows_total = 0;
+  uint64_t values_gen = 0, prec_gen = 0;
+  int prec_kind = PDH_PREC_NONE;
+  bool prec_ok = true;
+  enum { SOL_DINV, SOL_FLAG, SOL_R, SOL_Z, SOL_P, SOL_Q, SOL_PART, SOL_SCAL, SOL_N };
+  Scratch sol[SOL_N];
+  double *pinned = nullptr;
+  template <class T>
+  T *sol_get(int i, size_t count)
+  {
+    Scratch &s = sol[i];
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    if (bytes > s.bytes)
+      {
+        if (s.p)
+          (void)hipFree(s.p);
+        s.p = nullptr;
+        s.bytes = 0;
+        if (hipMalloc(&s.p, bytes) != hipSuccess)
+          return nullptr;
+        s.bytes = bytes;
+      }
+    return static_cast<T *>(s.p);
+  }
+  void free_solver()
+  {
+    for (auto &s : sol)
+      {
+        if (s.p)
+          (void)hipFree(s.p);
+        s = Scratch{};
+      }
+  }
   // cached multi-index table of pdh_shape_values (per dim/degree/basis)
   int shape_key = -1;
   int32_t *d_shape_midx = nullptr;
@@ -306,7 +347,10 @@ static void free_problem(pdh_ctx *ctx)
     (void)hipFree(p);
   ctx->allocs.clear();
   ctx->drop_graph();
+  ctx->free_solver();
   ctx->has_problem = false;
+  ctx->d_blk_ptr = nullptr;
+  ctx->d_blk_dof = nullptr;
   ctx->d_ap_src = nullptr;
   ctx->d_bd_rng = nullptr;
   ctx->d_mtab = nullptr;
@@ -434,6 +478,8 @@ extern "C" void pdh_destroy(pdh_ctx *ctx)
       (void)hipFree(sc.p);
   if (ctx->d_shape_midx)
     (void)hipFree(ctx->d_shape_midx);
+  if (ctx->pinned)
+    (void)hipHostFree(ctx->pinned);
   for (auto &ev : ctx->events)
     if (ev)
       (void)hipEventDestroy(ev);
@@ -480,6 +526,10 @@ struct Packed
   PdhBasisTab tab;
   std::vector<int32_t> own_agg, own_row, row_len, diag_L, it_own, it_nbr, it_pcnt, it_pos, it_nbr_slot, it_pos_t;
   std::vector<int64_t> row_base, vq_ptr, ap_ptr, it_pbeg;
+  // per owned slot: first global dof of every coupled block in value order (CSR; pdh_solve.h), and the longest row
+  std::vector<int64_t> blk_ptr{0};
+  std::vector<int32_t> blk_dof;
+  int max_row_len = 0;
   dvec vq_x, vq_w;
   // Own-side face points are NOT built on the host: set_problem uploads the caller's face arrays as they are and a kernel
   // (pdh_exchange.hip: k_pack_faces) writes the per-polytope runs in HBM from these tables - one entry per run, owned slots
@@ -813,6 +863,10 @@ static int pack_problem(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begin, i
           return fail(ctx, PDH_EINVAL, "rows of one polytope must have equal length");
       K.row_base.push_back(r0 - val_base);
       K.row_len.push_back((int32_t)rl);
+      for (const auto &b : blocks)
+        K.blk_dof.push_back(p->dof_offset[b.second]);
+      K.blk_ptr.push_back((int64_t)K.blk_dof.size());
+      K.max_row_len = std::max(K.max_row_len, (int)rl);
       int own_rank = 0;
       for (size_t t = 0; t < blocks.size(); ++t)
         if (blocks[t].second == a)
@@ -2441,6 +2495,8 @@ static int upload_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
   PDH_UP(K.it_pos, D.it_pos);
   PDH_UP(K.it_nbr_slot, D.it_nbr_slot);
   PDH_UP(K.it_pos_t, D.it_pos_t);
+  PDH_UP(K.blk_ptr, ctx->d_blk_ptr);
+  PDH_UP(K.blk_dof, ctx->d_blk_dof);
   if (K.ghost)
     {
       PDH_UP(K.r21_src, ctx->d_r21_src);
@@ -2502,6 +2558,8 @@ static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
   for (size_t r = 0; r < K.run_ap.size(); ++r)
     ctx->face_runs.push_back({K.run_ap[r], K.run_fq[r], K.run_cnt[r], K.run_bdry[r], K.run_slot[r]});
   ctx->n_rows_owned = (int64_t)K.n_owned * K.n;
+  ctx->n_rows_total = p->n_rows;
+  ctx->max_row_len = K.max_row_len;
   ctx->n_agg_total = p->n_agg;
   // executed work: k-steps of 4 points per chunk (64 points in k_diag for NT >= 3, else 32; 32 in k_offdiag)
   const int64_t i_sym = sched_instr_rt(K.NT, K.LB, true), i_full = sched_instr_rt(K.NT, K.LB, false);
@@ -2633,6 +2691,7 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_problem(ctx);
+  ++ctx->values_gen;
   struct FreeUnlessDone // every exit before the end leaves no problem resident
   {
     pdh_ctx *ctx;
@@ -2736,6 +2795,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
     return fail(nullptr, PDH_EINVAL, "ctx is NULL");
   if (!ctx->has_problem)
     return fail(ctx, PDH_ESTATE, "pdh_assemble_device called before pdh_set_problem");
+  ++ctx->values_gen;
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   pdh_launch_fn fn = ctx->tiled ? nullptr : g_launch[ctx->group];
   const int dim = ctx->dev.dim, n1d = ctx->dev.n1d, nt = ctx->NT, lb = ctx->LB;
@@ -2920,6 +2980,7 @@ extern "C" int pdh_exchange_apply(pdh_ctx *ctx, const double *d_recv)
 {
   if (!ctx || !ctx->has_problem || !ctx->problem_ghost)
     return fail(ctx, PDH_ESTATE, "no problem resident in PDH_EXCHANGE_GHOST mode");
+  ++ctx->values_gen;
   if (ctx->n_recv == 0)
     return PDH_OK;
   if (!d_recv)
@@ -3420,4 +3481,235 @@ extern "C" int pdh_problem_stats(pdh_ctx *ctx, int64_t *stats)
   stats[6] = (int64_t)ctx->lds_diag;
   stats[7] = (int64_t)ctx->lds_off;
   return PDH_OK;
+}
+
+// ---- solving with the resident matrix (pdh_solve.hip) -----------------------------------------------------------------
+static PdhSolveArgs solve_args(const pdh_ctx *ctx)
+{
+  PdhSolveArgs A;
+  A.values = ctx->dev.values;
+  A.row_base = ctx->dev.row_base;
+  A.row_len = ctx->dev.row_len;
+  A.diag_L = ctx->dev.diag_L;
+  A.own_row = ctx->dev.own_row;
+  A.blk_ptr = ctx->d_blk_ptr;
+  A.blk_dof = ctx->d_blk_dof;
+  A.n = ctx->dev.n;
+  A.diag_first = ctx->dev.diag_first;
+  A.n_owned = ctx->n_owned;
+  A.max_row_len = ctx->max_row_len;
+  return A;
+}
+
+static bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
+{
+  const char *pa = static_cast<const char *>(a), *pb = static_cast<const char *>(b);
+  return pa < pb + nb * (int64_t)sizeof(double) && pb < pa + na * (int64_t)sizeof(double);
+}
+
+static constexpr int PDH_VMULT_LDS_CAP = 64 * 1024; // column set of one polytope in LDS (8192 columns)
+
+static int vmult_checks(pdh_ctx *ctx, const void *x, const void *y)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_vmult called before pdh_set_problem");
+  if (!x || !y)
+    return fail(ctx, PDH_EINVAL, "x and y are required");
+  if (overlap(x, ctx->n_rows_total, y, ctx->n_rows_owned))
+    return fail(ctx, PDH_EINVAL, "x and y overlap");
+  if ((int64_t)ctx->max_row_len * (int64_t)sizeof(double) > PDH_VMULT_LDS_CAP)
+    return fail(ctx, PDH_EUNSUPPORTED, "a row has more than 8192 entries (the column set of a polytope must fit 64 KB of LDS)");
+  return PDH_OK;
+}
+
+extern "C" int pdh_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y)
+{
+  PDH_TRY(vmult_checks(ctx, d_x, d_y));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, d_y, nullptr, ctx->stream));
+  return PDH_OK;
+}
+
+extern "C" int pdh_vmult(pdh_ctx *ctx, const double *x, double *y)
+{
+  PDH_TRY(vmult_checks(ctx, x, y));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  double *d_x = static_cast<double *>(ctx->scratch_get(0, std::max<int64_t>(ctx->n_rows_total, 1) * sizeof(double)));
+  double *d_y = static_cast<double *>(ctx->scratch_get(1, std::max<int64_t>(ctx->n_rows_owned, 1) * sizeof(double)));
+  if (!d_x || !d_y)
+    return fail(ctx, PDH_EDEVICE, "pdh_vmult: out of device memory");
+  PDH_HIP(ctx, hipMemcpyAsync(d_x, x, ctx->n_rows_total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PDH_TRY(pdh_vmult_device(ctx, d_x, d_y));
+  PDH_HIP(ctx, hipMemcpyAsync(y, d_y, ctx->n_rows_owned * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PDH_OK;
+}
+
+extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_setup_preconditioner called before pdh_set_problem");
+  if (kind != PDH_PREC_NONE && kind != PDH_PREC_JACOBI && kind != PDH_PREC_BLOCK_JACOBI)
+    return fail(ctx, PDH_EINVAL, "kind must be PDH_PREC_NONE, PDH_PREC_JACOBI or PDH_PREC_BLOCK_JACOBI");
+  if (kind == PDH_PREC_BLOCK_JACOBI && ctx->dev.n > 64)
+    return fail(ctx, PDH_EUNSUPPORTED, "block Jacobi needs at most 64 dofs per polytope (use PDH_PREC_JACOBI)");
+  ctx->prec_kind = kind;
+  ctx->prec_gen = ctx->values_gen;
+  ctx->prec_ok = false; // until the set-up below has succeeded
+  if (kind == PDH_PREC_NONE)
+    {
+      ctx->prec_ok = true;
+      return PDH_OK;
+    }
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t n = ctx->dev.n;
+  double *dinv = ctx->sol_get<double>(pdh_ctx::SOL_DINV, kind == PDH_PREC_BLOCK_JACOBI ? ctx->n_owned * n * n : ctx->n_rows_owned);
+  int32_t *flag = ctx->sol_get<int32_t>(pdh_ctx::SOL_FLAG, ctx->n_owned);
+  if (!dinv || !flag)
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_preconditioner: out of device memory");
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, kind == PDH_PREC_BLOCK_JACOBI ? pdh_launch_block_inverse(&A, dinv, flag, ctx->stream)
+                                             : pdh_launch_diag_inverse(&A, dinv, flag, ctx->stream));
+  std::vector<int32_t> h_flag((size_t)ctx->n_owned);
+  if (ctx->n_owned)
+    PDH_HIP(ctx, hipMemcpyAsync(h_flag.data(), flag, h_flag.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int s = 0; s < ctx->n_owned; ++s)
+    if (h_flag[s])
+      { // slots are in polytope order: the first flagged slot is the lowest polytope number
+        int32_t agg = -1;
+        PDH_HIP(ctx, hipMemcpy(&agg, ctx->dev.own_agg + s, sizeof(int32_t), hipMemcpyDeviceToHost));
+        return fail(ctx, PDH_EINVAL,
+                    kind == PDH_PREC_BLOCK_JACOBI
+                      ? "block Jacobi: the diagonal block of polytope " + std::to_string(agg) + " is not positive definite"
+                      : "Jacobi: a diagonal entry of polytope " + std::to_string(agg) + " is zero or not finite");
+      }
+  ctx->prec_ok = true;
+  return PDH_OK;
+}
+
+static int prec_checks(pdh_ctx *ctx)
+{
+  if (ctx->prec_kind != PDH_PREC_NONE && (!ctx->prec_ok || ctx->prec_gen != ctx->values_gen))
+    return fail(ctx, PDH_ESTATE, ctx->prec_ok ? "the values changed since pdh_setup_preconditioner: set it up again"
+                                              : "the last pdh_setup_preconditioner failed");
+  return PDH_OK;
+}
+
+extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *d_z)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_precondition_device called before pdh_set_problem");
+  if (!d_r || !d_z)
+    return fail(ctx, PDH_EINVAL, "r and z are required");
+  PDH_TRY(prec_checks(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_APPLY, ctx->prec_kind, static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p),
+                                    nullptr, nullptr, nullptr, nullptr, const_cast<double *>(d_r), d_z, nullptr, nullptr, ctx->stream));
+  return PDH_OK;
+}
+
+extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const double *d_b, double *d_x, pdh_cg_result *res)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_solve_cg called before pdh_set_problem");
+  if (!c || !d_b || !d_x || !res)
+    return fail(ctx, PDH_EINVAL, "control, b, x and result are required");
+  if (c->max_iter < 0 || !(c->rel_tol >= 0.0) || !(c->abs_tol >= 0.0))
+    return fail(ctx, PDH_EINVAL, "max_iter, rel_tol and abs_tol must be non-negative");
+  if (ctx->problem_ghost)
+    return fail(ctx, PDH_EUNSUPPORTED, "pdh_solve_cg: the problem was set in PDH_EXCHANGE_GHOST mode; the solver runs on a context that "
+                                       "owns all rows with PDH_EXCHANGE_NONE (no distributed Krylov solver)");
+  if (ctx->n_rows_owned != ctx->n_rows_total)
+    return fail(ctx, PDH_EUNSUPPORTED, "pdh_solve_cg: the context owns rows " + std::to_string(ctx->n_rows_owned) + " of " +
+                                         std::to_string(ctx->n_rows_total) + "; the solver needs all rows in one context (no distributed "
+                                                                             "Krylov solver)");
+  if (overlap(d_b, ctx->n_rows_total, d_x, ctx->n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  PDH_TRY(prec_checks(ctx));
+  if ((int64_t)ctx->max_row_len * (int64_t)sizeof(double) > PDH_VMULT_LDS_CAP)
+    return fail(ctx, PDH_EUNSUPPORTED, "a row has more than 8192 entries (the column set of a polytope must fit 64 KB of LDS)");
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t N = ctx->n_rows_owned;
+  double *r = ctx->sol_get<double>(pdh_ctx::SOL_R, N), *z = ctx->sol_get<double>(pdh_ctx::SOL_Z, N);
+  double *p = ctx->sol_get<double>(pdh_ctx::SOL_P, N), *q = ctx->sol_get<double>(pdh_ctx::SOL_Q, N);
+  double *part = ctx->sol_get<double>(pdh_ctx::SOL_PART, (size_t)PDH_CG_NPART * ctx->n_owned);
+  double *scal = ctx->sol_get<double>(pdh_ctx::SOL_SCAL, PDH_CG_NSCALARS);
+  if (!ctx->pinned && hipHostMalloc((void **)&ctx->pinned, 2 * sizeof(double), hipHostMallocDefault) != hipSuccess)
+    ctx->pinned = nullptr;
+  if (!r || !z || !p || !q || !part || !scal || !ctx->pinned)
+    return fail(ctx, PDH_EDEVICE, "pdh_solve_cg: out of device memory");
+  const double *dinv = static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p);
+  const int kind = ctx->prec_kind;
+  const PdhSolveArgs A = solve_args(ctx);
+  hipStream_t st = ctx->stream;
+  // r = b - A x0, z = P^-1 r, p = z
+  PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, q, nullptr, st));
+  PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, d_b, q, nullptr, nullptr, r, z, scal, part, st));
+  PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 0, scal, st));
+  PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
+  PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + PDH_CG_RR, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  PDH_HIP(ctx, hipStreamSynchronize(st));
+  double rr = ctx->pinned[0];
+  const double bnorm = std::sqrt(ctx->pinned[1]);
+  const double stop = std::max(c->abs_tol, c->rel_tol * bnorm);
+  res->residual0 = std::sqrt(rr);
+  int it = 0;
+  // the loop of examples/host_solver.h: test, then q = A p, alpha, x and r, z, beta, p.  Only ||r||^2 crosses PCIe (8 bytes, pinned).
+  for (; it < c->max_iter && std::sqrt(rr) > stop; ++it)
+    {
+      PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * ctx->n_owned, st));
+      PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 1, scal, st));
+      PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, d_x, r, z, scal, part, st));
+      PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 2, scal, st));
+      PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
+      PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + PDH_CG_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+      PDH_HIP(ctx, hipStreamSynchronize(st));
+      rr = ctx->pinned[0];
+    }
+  res->iterations = it;
+  res->residual = std::sqrt(rr);
+  if (!(res->residual <= stop))
+    return fail(ctx, PDH_ENOCONV, "pdh_solve_cg: no convergence in " + std::to_string(it) + " iterations (||r|| = " +
+                                    std::to_string(res->residual) + ", bound " + std::to_string(stop) + ")");
+  return PDH_OK;
+}
+
+extern "C" int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *c, const double *b, double *x, pdh_cg_result *res)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_solve_cg called before pdh_set_problem");
+  if (!b || !x)
+    return fail(ctx, PDH_EINVAL, "b and x are required");
+  if (overlap(b, ctx->n_rows_total, x, ctx->n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t N = ctx->n_rows_total;
+  double *d_b = static_cast<double *>(ctx->scratch_get(0, std::max<int64_t>(N, 1) * sizeof(double)));
+  double *d_x = static_cast<double *>(ctx->scratch_get(1, std::max<int64_t>(N, 1) * sizeof(double)));
+  if (!d_b || !d_x)
+    return fail(ctx, PDH_EDEVICE, "pdh_solve_cg: out of device memory");
+  PDH_HIP(ctx, hipMemcpyAsync(d_b, b, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PDH_HIP(ctx, hipMemcpyAsync(d_x, x, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = pdh_solve_cg_device(ctx, c, d_b, d_x, res);
+  if (rc != PDH_OK && rc != PDH_ENOCONV)
+    return rc;
+  const std::string msg = ctx->err;
+  PDH_HIP(ctx, hipMemcpyAsync(x, d_x, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (rc == PDH_ENOCONV)
+    ctx->err = msg;
+  return rc;
 }

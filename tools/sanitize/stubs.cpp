@@ -28,4 +28,11 @@ extern "C" int pdh_tiled_has_kind(int dim,int n1d,int){return dim == 3 && n1d >=
 extern "C" int pdh_terms_has_kind(int n1d,int basis){return (n1d < 2 || n1d > 4 || basis < 0 || basis > 1) ? 0 : (n1d == 4 && basis == 0) ? 2 : 1;}
 // (any size that fits the LDS budget: the host tables of the term kernels are built in full)
 extern "C" int pdh_terms_lds_bytes(int,int,int,int,int,int,int,int){return 1024;}
+struct PdhSolveArgs;
+extern "C" hipError_t pdh_launch_vmult(const PdhSolveArgs*,const double*,double*,double*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_block_inverse(const PdhSolveArgs*,double*,int32_t*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_diag_inverse(const PdhSolveArgs*,double*,int32_t*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_cg_update(const PdhSolveArgs*,int,int,const double*,const double*,const double*,const double*,double*,double*,double*,const double*,double*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_cg_direction(int64_t,int,const double*,double*,const double*,hipStream_t){return hipSuccess;}
+extern "C" hipError_t pdh_launch_cg_finalise(const double*,int,int,double*,hipStream_t){return hipSuccess;}
 extern "C" int pdh_terms_task_doubles(int maxsf,int maxcell,int pm){return (2*maxsf+3*maxcell)*3*pm+2*maxsf;}
