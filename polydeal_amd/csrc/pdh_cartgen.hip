@@ -9,6 +9,7 @@
 // One thread per point, structure-of-arrays output in the layout the caller's arrays would have had: 0.9 GB for the bench mesh are
 // written at HBM speed instead of being built by the host (0.2 s) and pushed through PCIe (30 ms).
 #include "pdh_kernels.h"
+#include "pdh_launch.h"
 
 struct PdhRule
 {

@@ -12,6 +12,7 @@
 // LDS traffic; the polytope's coefficients are read as LDS broadcasts at compile-time offsets.  HBM-bound: 8 (d + 1) bytes
 // read and 8 (1 + d) written per point.
 #include "pdh_kernels.h"
+#include "pdh_launch.h"
 
 namespace pdh
 {

@@ -7,6 +7,7 @@
 // after the transport this kernel puts them in place: M21 blocks are stored (nothing else contributes to A[Q,P]), the M22
 // sums are added to A[Q,Q], all contributions of one polytope by one wave in a fixed order (bit-reproducible, no atomics).
 #include "pdh_kernels.h"
+#include "pdh_launch.h"
 
 __global__ void __launch_bounds__(PDH_WAVE) k_ghost_apply(const PdhDev P, const double *__restrict__ recv, const int n_r21,
                                                           const int64_t *__restrict__ r21_src, const int64_t *__restrict__ r21_dst,
@@ -103,7 +104,7 @@ extern "C" hipError_t pdh_launch_checksum(const double *values, int64_t n, doubl
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Set-up: own-side face points of every (polytope, face) run, written in HBM from the caller's face arrays (each face
-// stored once).  One wave per run.  Weights / signs as the assembly kernels expect them (pdh_capi.cpp: Packed::pk_*):
+// stored once).  One wave per run.  Weights / signs as the assembly kernels expect them (pdh_plan.h: Packed::pk_*):
 //   boundary run: w_self = 2 JxW, sigma / 2, w_cross = 0; interior: w_self = JxW of the own side, w_cross = JxW of side 1,
 //   normal = outward normal of the owning polytope (sign flipped when it is side 1 of the face).
 // ---------------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // term) and k_offdiag for the combos of that group (pdh_combos.h) and exposes a plain launcher.
 #include "pdh_combos.h"
 #include "pdh_kernels.h"
+#include "pdh_launch.h"
 
 #ifndef PDH_GROUP
 #error "compile with -DPDH_GROUP=0..7"

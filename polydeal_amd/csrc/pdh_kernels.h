@@ -37,8 +37,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#define PDH_MAX_N1D 8
-#define PDH_WAVE 64
+#include "pdh_dev.h"
 
 // Ordering of LDS traffic inside ONE wave.  Every kernel of this library runs single-wave workgroups; the lanes of a wave
 // exchange data through LDS (records, staging tiles).  The LDS unit executes the DS instructions of a wave in issue
@@ -55,48 +54,6 @@
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                                        \
     }                                                                                                               \
   while (0)
-
-struct PdhBasisTab
-{
-  double coef[PDH_MAX_N1D][PDH_MAX_N1D]; // coef[k][m]: monomial coefficients of 1-D basis function k
-};
-
-struct PdhDev
-{
-  int32_t dim, n, n1d, diag_first;
-  double reaction_c;
-  const double *bbox;   // [n_agg][2][dim]
-  const int32_t *midx;  // [16*NT] packed multi-index (k0 | k1<<8 | k2<<16), 0xffffffff = dead
-  // volume quadrature of the owned polytopes (SoA), indexed by owned slot
-  const int64_t *vq_ptr;
-  const double *vq_x;
-  int64_t vq_stride;
-  const double *vq_w;
-  // own-side face points, packed per owned polytope
-  const int64_t *ap_ptr; // [n_owned+1]
-  const double *ap_x;    // [dim][P]
-  const double *ap_n;    // [dim][P] outward normal of the owning polytope
-  int64_t ap_stride;
-  const double *ap_wself;  // [P] JxW used by the diagonal block (2 JxW on the boundary)
-  const double *ap_wcross; // [P] JxW used by the coupling block (JxW of side 1)
-  const double *ap_sig;    // [P] sigma (sigma/2 on the boundary)
-  // diagonal-block items
-  const int32_t *own_agg;  // [n_owned]
-  const int64_t *row_base; // [n_owned] value offset of the polytope's first row
-  const int32_t *row_len;  // [n_owned] entries per row
-  const int32_t *diag_L;   // [n_owned] ascending column position of the own block inside the row
-  const int32_t *own_row;  // [n_owned] first dof row of the polytope, relative to the owned row range
-  // coupling-block items: one per interior face with at least one owned side
-  const int32_t *it_own;  // owned slot of P (the side whose packed points are used)
-  const int32_t *it_nbr;  // neighbour polytope id Q
-  const int64_t *it_pbeg; // first packed point
-  const int32_t *it_pcnt; // number of points
-  const int32_t *it_pos;  // position of Q's block inside P's rows (diag-first shift included)
-  const int32_t *it_nbr_slot; // owned slot of Q, or -1: A[Q,P] = A[P,Q]^T is then not written here
-  const int32_t *it_pos_t;    // position of P's block inside Q's rows
-  double *values;
-  PdhBasisTab tab;
-};
 
 // Experiment switches for tools/ab_bench.py (never defined in the shipped build): time the kernels without their
 // epilogue (-DPDH_EXP_NOSTORE) or without their accumulation loops (-DPDH_EXP_NOCOMPUTE).  Measured on the
@@ -995,19 +952,5 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_offdiag(const PdhDev P, const i
         store_strip<false>(P.values, qbase, qlen, post, 0, strip, ncol_pad, s, n, lane);
       });
     }
-}
-
-// LDS bytes needed by the two kernels (host side helper).
-inline size_t lds_bytes_diag(int dim, int n1d, int nt)
-{
-  const size_t recs = (size_t)(nt >= 3 ? PDH_WAVE : 32) * (dim * n1d * 2 + 2 + 2 + dim) * sizeof(double); // CH-point chunks
-  const size_t strip = (size_t)16 * (16 * nt + 2) * sizeof(double);
-  return recs > strip ? recs : strip;
-}
-inline size_t lds_bytes_offdiag(int dim, int n1d, int nt)
-{
-  const size_t recs = (size_t)32 * (2 * (dim * n1d * 2 + 2) + 2 + dim) * sizeof(double); // 32-point chunks
-  const size_t strip = (size_t)16 * (16 * nt + 2) * sizeof(double);
-  return recs > strip ? recs : strip;
 }
 } // namespace pdh

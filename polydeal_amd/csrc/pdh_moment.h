@@ -25,6 +25,7 @@
 // pdh_kernels.h); this file only changes the order of summation.
 #pragma once
 #include "pdh_kernels.h"
+#include "pdh_moment_tables.h"
 
 // experiment switches (tools/ab_bench.py; never defined in the shipped build, results are garbage with them):
 // -DPDHM_EXP=1 no per-face tables, 2 no moment accumulation, 3 no contraction, 4 no stores
@@ -48,24 +49,6 @@
 namespace pdhm
 {
 using pdh::static_for;
-
-template <int N1D>
-struct MT
-{
-  static constexpr int NA = 2 * N1D - 1; // Legendre modes 0 .. 2p
-  static constexpr int NAP = NA + 1;     // padded (even: 16-byte rows)
-  static constexpr int NG = 2 * N1D;     // Gauss points of the per-face table rule: exact to degree 4p+3 >= 4p
-  static constexpr int PAIRS = N1D * N1D;
-  static constexpr int TAB = PAIRS * NAP; // one expansion table [k][l][NAP] in the global buffer
-  // In LDS the table rows and the T2 rows use a stride of NAP + 2 doubles: with 64-byte rows the 16 rows a wave
-  // touches in one ds_read_b128 (lanes differing in two 1-D indices) fall on four bank groups only - a 16-way conflict
-  // that made the contraction 8x slower than its instruction count; 80-byte rows are conflict-free.
-  static constexpr int RS = NAP + 2;
-  static constexpr int LTAB = PAIRS * RS;
-  // layout of the device table buffer (doubles); filled by pdh_capi.cpp:build_moment_tables
-  static constexpr int OFF_E = 0, OFF_D = TAB, OFF_FS = 2 * TAB, OFF_GX = 3 * TAB, OFF_GL = OFF_GX + NG /* [NA][NG] */,
-                       OFF_BV = OFF_GL + NA * NG /* [N1D][NG] */, OFF_BD = OFF_BV + N1D * NG, SIZE = OFF_BD + N1D * NG;
-};
 
 // L_a(x) = sqrt(2a+1) P_a(2x-1), a = 0 .. NA-1, by the three-term recurrence of the ORTHONORMAL polynomials
 //   L_{k+1} = A_k t L_k - C_k L_{k-1},  t = 2x-1,  A_k = sqrt((2k+1)(2k+3))/(k+1),  C_k = k/(k+1) sqrt((2k+3)/(2k-1))

@@ -2,6 +2,7 @@
 #include <cstdlib>
 #include "pdh_moment.h"
 #include "pdh_rows.h"
+#include "pdh_launch.h"
 
 // which: 0 = diagonal blocks (count = owned polytopes), 1 = coupling blocks (count = interior-face items)
 extern "C" hipError_t pdh_launch_moment(int n1d, int which, const PdhDev *P, const double *mtab, int count, hipStream_t stream)
@@ -32,17 +33,6 @@ extern "C" hipError_t pdh_launch_moment(int n1d, int which, const PdhDev *P, con
   PDH_MOM_CASE(2) PDH_MOM_CASE(3) PDH_MOM_CASE(4)
 #undef PDH_MOM_CASE
   return hipErrorInvalidValue;
-}
-
-extern "C" int pdh_moment_table_doubles(int n1d)
-{
-  switch (n1d)
-    {
-    case 2: return pdhm::MT<2>::SIZE;
-    case 3: return pdhm::MT<3>::SIZE;
-    case 4: return pdhm::MT<4>::SIZE;
-    }
-  return 0;
 }
 
 // Row kernel (pdh_rows.h): one wave per owned polytope writes all blocks of its rows; FE_DGQ(3) or FE_AggloDGP(3) in 3-D,
@@ -89,7 +79,7 @@ extern "C" hipError_t pdh_launch_rows(const PdhDev *P, const PdhRows *R, const d
     const size_t granules = (lds + pad + 1279) / 1280 * 1280;
     const int fit_lds = (int)(160 * 1024 / granules);
     // degree 3: the instantiation without general-point paths when the host verified tensor rules everywhere
-    // (PdhRows::tensor_only, pdh_capi.cpp: rows_kind_applies)
+    // (PdhRows::tensor_only, pdh_plan.cpp: rows_kind_applies)
     auto go = [&](auto general_, auto shifted_, auto multi_) {
       constexpr bool G = decltype(general_)::value, S = decltype(shifted_)::value, MU = decltype(multi_)::value;
       static thread_local size_t occ_lds = ~(size_t)0; // (per instantiation and thread)
@@ -163,17 +153,3 @@ extern "C" hipError_t pdh_launch_rows(const PdhDev *P, const PdhRows *R, const d
     launch(integral_constant<int, 2>{}, integral_constant<int, 1>{});
   return rc;
 }
-extern "C" int pdh_rows_n_dofs(int n1d, int basis)
-{
-  switch (n1d * 2 + (basis ? 1 : 0))
-    {
-    case 8: return pdhr::RowsKind<4, 0>::NF;
-    case 9: return pdhr::RowsKind<4, 1>::NF;
-    case 6: return pdhr::RowsKind<3, 0>::NF;
-    case 7: return pdhr::RowsKind<3, 1>::NF;
-    case 4: return pdhr::RowsKind<2, 0>::NF;
-    case 5: return pdhr::RowsKind<2, 1>::NF;
-    }
-  return 0;
-}
-extern "C" int pdh_rows_max_faces(void) { return pdhr::MAXF; }

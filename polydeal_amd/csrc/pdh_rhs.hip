@@ -12,6 +12,7 @@
 //           from the full 1-D records.
 // Reads 8 (d + 2) bytes per volume point; bound by LDS reads + multiply-adds of the pair loop, not by HBM.
 #include "pdh_kernels.h"
+#include "pdh_launch.h"
 
 namespace pdh
 {

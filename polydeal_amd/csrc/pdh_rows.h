@@ -181,8 +181,6 @@ using pdh::static_for;
 using pdhm::d2_t;
 typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
 
-constexpr int ROWS_HDR = 12, ROWS_MAXE = 16, ROWS_ENT = 12, ROWS_REC = ROWS_HDR + ROWS_MAXE * ROWS_ENT; // per-slot record
-constexpr int MAXF = 6;  // INTERIOR faces per polytope the LDS layout provides for (6: 20.3 KB per wave = 8 waves per CU)
 constexpr int FREC = 33; // face record: L_i[8], (s_t L_j)[3][8], pad (odd stride)
 constexpr int FCH = 32;  // face points per chunk
 constexpr int FSTEP = 4 * FREC * 8;
@@ -196,7 +194,7 @@ struct RowsKind
 {
   static constexpr bool SMALL = !(N1D == 4 && BASIS == 0);
   static constexpr int NA = 2 * N1D - 1;
-  static constexpr int NF = BASIS == 0 ? N1D * N1D * N1D : N1D * (N1D + 1) * (N1D + 2) / 6; // functions
+  static constexpr int NF = rows_n_functions(N1D, BASIS);                                   // functions
   static constexpr int NS = BASIS == 0 ? N1D * N1D : N1D * (N1D + 1) / 2;                   // pairs of tangential digits
   static constexpr int SS = SMALL ? ((NS * NS > 64 ? NS * NS : 64) + 7) / 8 * 8 : 64; // per-face slot: 8x8 moments, later S
   // task vectors of P2 (tensor sub-face rules): [64 tasks][self | cross], 8 + 8 doubles per task - packed to NA + NA (odd
@@ -353,7 +351,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
   auto rl_d = [](double v, int t) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), t), __builtin_amdgcn_readlane(__double2loint(v), t));
   };
-  // Per-slot record (pdh_capi.cpp:build_rows_tables): ROWS_HDR header doubles, then ROWS_MAXE face entries of ROWS_ENT
+  // Per-slot record (pdh_plan.cpp: build_rows_tables): ROWS_HDR header doubles, then ROWS_MAXE face entries of ROWS_ENT
   // doubles (neighbour boxes included) - ONE round of loads per polytope, requested a whole polytope ahead: under the store
   // traffic of this kernel a dependent global load takes ~7k cycles, and the chain slot -> face table -> neighbour boxes
   // used to cost three of them at the head of every polytope.
@@ -361,7 +359,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
   {
     double e[ROWS_ENT]; // lanes 0 .. maxe-1: the face entry; lanes maxe .. maxe+ROWS_HDR-1: e[0] = header value
   };
-  const int hb = maxe; // first header lane (maxe <= 48, pdh_capi.cpp: build_rows_tables)
+  const int hb = maxe; // first header lane (maxe <= 48, pdh_plan.cpp: build_rows_tables)
   auto load_meta = [&](int s_) {
     Meta m;
     const double *r = Rw.meta + (int64_t)s_ * (ROWS_HDR + maxe * ROWS_ENT);

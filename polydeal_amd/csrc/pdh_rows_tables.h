@@ -1,6 +1,20 @@
-// pdh_rows_tables.h — the PdhRows struct shared by the row kernel (pdh_rows.h, device) and pdh_capi.cpp (host).
+// pdh_rows_tables.h — the PdhRows struct and the layout constants shared by the row kernel (pdh_rows.h, device) and the host
+// (pdh_plan.cpp builds the tables, pdh_capi.cpp uploads them).  Compiles with and without HIP.
 #pragma once
 #include <stdint.h>
+
+#include "pdh_dev.h"
+
+namespace pdhr
+{
+// per-slot record (pdh_plan.cpp: build_rows_tables): ROWS_HDR header doubles, then one entry of ROWS_ENT doubles per face - ROWS_MAXE
+// of them unless PdhRows::multi
+constexpr int ROWS_HDR = 12, ROWS_MAXE = 16, ROWS_ENT = 12, ROWS_REC = ROWS_HDR + ROWS_MAXE * ROWS_ENT;
+constexpr int MAXF = 6; // INTERIOR faces per polytope the LDS layout provides for (6: 20.3 KB per wave = 8 waves per CU)
+// functions of the element of a kind (pdh_rows.h: RowsKind); BASIS = 0: all (k0,k1,k2) < N1D, 1: k0 + k1 + k2 <= p
+PDH_HD constexpr int rows_n_functions(int n1d, int basis) { return basis == 0 ? n1d * n1d * n1d : n1d * (n1d + 1) * (n1d + 2) / 6; }
+} // namespace pdhr
+
 struct PdhRows
 {
   const int32_t *fr_ptr;   // [n_owned+1] faces of every owned polytope: boundary faces first, then ascending block rank

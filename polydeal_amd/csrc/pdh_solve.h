@@ -1,14 +1,13 @@
 // pdh_solve.h — operator apply, preconditioners and the vector kernels of conjugate gradients on the RESIDENT matrix values
 // (pdh_solve.hip).  Shared by the kernels and the C ABI (pdh_capi.cpp); the host passes this struct by value.
 //
-// Layout walked (pdh_capi.cpp: Packed): owned slot s holds the n rows of one polytope, row i at values[row_base[s] + i * row_len[s]],
+// Layout walked (pdh_plan.h: Packed): owned slot s holds the n rows of one polytope, row i at values[row_base[s] + i * row_len[s]],
 // all of length row_len[s] = (number of coupled blocks) * n.  The blocks of a row are the polytope and its neighbours in ascending
 // column number (col_offset or dof_offset); blk_dof[blk_ptr[s] + t] is the first GLOBAL dof of the t-th of them, so the entry at
 // ascending position a = t * n + j multiplies x[blk_dof[blk_ptr[s] + t] + j] - whichever numbering orders the blocks.  diag_L[s] is
 // the ascending position of the own block.  In the deal.II layout (diag_first) row i stores its diagonal entry first and the entries
 // at ascending positions 0 .. diag_L + i - 1 one place later; the others stay where they are.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 struct PdhSolveArgs
@@ -50,19 +49,3 @@ enum PdhCgMode
   PDH_UPD_INIT = 1,  // r = b - q, z = P^-1 r; partials of r^T z, r^T r, b^T b
   PDH_UPD_STEP = 2   // x += alpha p, r -= alpha q, z = P^-1 r; partials of r^T z, r^T r
 };
-
-extern "C" {
-// y[own rows] = A x (x in the global dof numbering).  part (may be NULL): per slot, sum_i y_i x_i over the slot's own rows.
-hipError_t pdh_launch_vmult(const PdhSolveArgs *A, const double *x, double *y, double *part, hipStream_t stream);
-// inverses of the n x n diagonal blocks (n <= 64) into dinv [n_owned][n][n]; flag[s] = 1 where the block is not positive definite
-hipError_t pdh_launch_block_inverse(const PdhSolveArgs *A, double *dinv, int32_t *flag, hipStream_t stream);
-// inverse of the diagonal into dinv [n_owned * n]; flag[s] = 1 where a diagonal entry of the slot is zero or not finite
-hipError_t pdh_launch_diag_inverse(const PdhSolveArgs *A, double *dinv, int32_t *flag, hipStream_t stream);
-// the fused vector kernel (PdhCgMode; kind = PDH_PREC_*); vectors indexed by owned row
-hipError_t pdh_launch_cg_update(const PdhSolveArgs *A, int mode, int kind, const double *dinv, const double *b, const double *q,
-                                const double *p, double *x, double *r, double *z, const double *scal, double *part, hipStream_t stream);
-// p = z + beta p (init: p = z) over n_rows entries
-hipError_t pdh_launch_cg_direction(int64_t n_rows, int init, const double *z, double *p, const double *scal, hipStream_t stream);
-// one workgroup: partials -> scalars.  stage 0: rz, rr, bb;  1: pq, alpha;  2: rz, rr, beta
-hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, int stage, double *scal, hipStream_t stream);
-}

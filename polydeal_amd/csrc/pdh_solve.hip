@@ -4,6 +4,7 @@
 // Every sum has a fixed order: a lane adds its terms in index order, a wave adds its 64 lanes by a butterfly, the slots' partials
 // are added by ONE workgroup in slot order (k_cg_finalise).  No atomics: the same call on the same data gives the same bits.
 #include "pdh_solve.h"
+#include "pdh_launch.h"
 
 #include <hip/hip_runtime.h>
 

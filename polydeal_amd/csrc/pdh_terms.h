@@ -49,75 +49,7 @@ namespace pdht
 using pdh::static_for;
 typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
 
-constexpr int TERMS_HDR = 12, TERMS_ENT = 10;
-
-template <int N1D, int BASIS>
-struct Kind
-{
-  static constexpr int NF = BASIS == 0 ? N1D * N1D * N1D : N1D * (N1D + 1) * (N1D + 2) / 6; // functions
-  static constexpr int NS = BASIS == 0 ? N1D * N1D : N1D * (N1D + 1) / 2;                   // pairs (k1, k2) that occur
-  static constexpr int NSYM = N1D * (N1D + 1) / 2, FULL = N1D * N1D;
-  static constexpr int SYMS = NSYM | 1, FULLS = FULL | 1; // odd strides: the lane tasks of phase A write table after table
-  static constexpr int NSUB = 64 / NF > 0 ? 64 / NF : 1;  // subsets of the diagonal block's terms (lanes = NSUB x NF columns)
-  struct Dig
-  {
-    int k0, k1, k2;
-  };
-  // digits of function R (x fastest; BASIS 1: k0 + k1 + k2 <= p, pdh_basis.h: multi_indices)
-  __host__ __device__ static constexpr Dig dig(int R)
-  {
-    if (BASIS == 0)
-      return Dig{R % N1D, (R / N1D) % N1D, R / (N1D * N1D)};
-    int cnt = 0;
-    for (int iz = 0; iz < N1D; ++iz)
-      for (int iy = 0; iy < N1D - iz; ++iy)
-        for (int ix = 0; ix < N1D - iy - iz; ++ix)
-          {
-            if (cnt == R)
-              return Dig{ix, iy, iz};
-            ++cnt;
-          }
-    return Dig{0, 0, 0};
-  }
-  __host__ __device__ static constexpr int pair(int k1, int k2) { return BASIS == 0 ? k1 + N1D * k2 : k2 * N1D - k2 * (k2 - 1) / 2 + k1; }
-  __host__ __device__ static constexpr bool pair_ok(int k1, int k2) { return BASIS == 0 || k1 + k2 < N1D; }
-  __host__ __device__ static constexpr int sym(int k, int l) { return k <= l ? l * (l + 1) / 2 + k : k * (k + 1) / 2 + l; }
-};
-
-// LDS of a workgroup in doubles (host and device agree through this one function)
-__host__ __device__ constexpr int terms_rec_doubles(int maxruns) { return (TERMS_HDR + maxruns * TERMS_ENT + 1) & ~1; }
-// Two-phase tables (SPLIT): the D / M / K tables are needed by the diagonal block only, the X tables by the row pieces only.  Made
-// in one pass they cost FE_AggloDGP(3) on block polytopes 21 KB of LDS per wave = 7 resident waves per CU, 30-40 KB on METIS-like
-// agglomerates, and the kernel runs at the speed its occupancy allows; made one after the other - the X tables from the point data
-// still held in registers, behind the finished block - 13.7 KB = 11 waves, for 250 more VALU instructions per polytope (the bases
-// at the tangential points are evaluated twice): 0.384 -> 0.373 ms on the bench mesh, 0.71 -> 0.56 ms on its grown agglomerates
-// (profiles/r04_terms_split.txt).  The host takes the form that gives a polytope's workgroup more resident waves (PdhTerms::split).
-// (BLOCK_IN_LDS: the wave-per-polytope kernel leaves the diagonal block in LDS over the dead tables; the workgroup kernel of
-// pdh_terms_wg.h stores it from registers)
-template <int N1D, int BASIS, bool BLOCK_IN_LDS = true, bool SPLIT = false>
-__host__ __device__ constexpr int terms_lds_doubles(int maxruns, int maxsf, int maxsi, int maxcell)
-{
-  using K = Kind<N1D, BASIS>;
-  const int dg = (K::NF + 1) / 2 + ((K::NF + 1) / 2 & 1);
-  const int xa = maxsi * 3 * K::FULLS + ((maxsi * 3 * K::FULLS) & 1);
-  int da = maxsf * 3 * K::SYMS + maxcell * 6 * K::SYMS;
-  if (BLOCK_IN_LDS && SPLIT)
-    { // the X tables are made after the diagonal block and stand BEHIND it, over the D tables (dead by then)
-      const int xb = K::NF * K::NF + xa;
-      da = da > xb ? da : xb;
-      return terms_rec_doubles(maxruns) + dg + da + (da & 1);
-    }
-  if (BLOCK_IN_LDS)
-    da = da > K::NF * K::NF ? da : K::NF * K::NF;
-  return terms_rec_doubles(maxruns) + dg + xa + da + (da & 1);
-}
-
-// A polytope's record of 1-D rules (PdhTerms::tdata): the points of every (sub-face, tangential direction) and (cell, direction) task
-// [task][x | w_self | w_cross][pmax], then per sub-face its plane coordinate and descriptor
-__host__ __device__ constexpr int terms_task_doubles(int maxsf, int maxcell, int pmax)
-{
-  return (2 * maxsf + 3 * maxcell) * pmax * 3 + 2 * maxsf;
-}
+// (TERMS_HDR / TERMS_ENT, Kind, terms_rec_doubles, terms_lds_doubles, terms_task_doubles: pdh_terms_tables.h, shared with the host)
 
 // Phase A of the term kernels: the lane tasks that build the small matrices of a polytope in LDS.  Shared by the wave-per-polytope
 // kernel below and the workgroup-per-polytope kernel of pdh_terms_wg.h.  PMAX: most points per direction of a rule (4 or 8): the

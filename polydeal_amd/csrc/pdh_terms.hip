@@ -2,53 +2,9 @@
 #include <cstdlib>
 #include "pdh_terms.h"
 #include "pdh_terms_wg.h"
+#include "pdh_launch.h"
 
-namespace
-{
-template <class F>
-bool for_kind(int n1d, int basis, F &&f)
-{
-  using std::integral_constant;
-  if (n1d == 4 && basis == 1)
-    f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
-  else if (n1d == 3 && basis == 0)
-    f(integral_constant<int, 3>{}, integral_constant<int, 0>{});
-  else if (n1d == 3 && basis == 1)
-    f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
-  else if (n1d == 2 && basis == 0)
-    f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
-  else if (n1d == 2 && basis == 1)
-    f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
-  else
-    return false;
-  return true;
-}
-} // namespace
-
-// 1 if the term kernel (pdh_terms.h, a wave per polytope) is instantiated for this element, 2: FE_DGQ(3), which has the
-// workgroup-per-polytope kernel of pdh_terms_wg.h instead
-extern "C" int pdh_terms_has_kind(int n1d, int basis)
-{
-  if (n1d == 4 && basis == 0)
-    return 2;
-  return for_kind(n1d, basis, [](auto, auto) {}) ? 1 : 0;
-}
-
-// dynamic LDS of a workgroup for the maxima of a resident problem, bytes (0: no such kind)
-// split: the two-phase form of the wave-per-polytope kernel (pdh_terms.h: SPLIT; ignored for the workgroup kernel)
-extern "C" int pdh_terms_lds_bytes(int n1d, int basis, int maxruns, int maxsf, int maxsi, int maxcell, int split, int task_pts)
-{
-  int bytes = 0;
-  (void)task_pts;
-  if (n1d == 4 && basis == 0)
-    return 8 * pdht::terms_lds_doubles<4, 0, false>(maxruns, maxsf, maxsi, maxcell);
-  for_kind(n1d, basis, [&](auto n_, auto b_) {
-    constexpr int N = decltype(n_)::value, B = decltype(b_)::value;
-    bytes = 8 * (split ? pdht::terms_lds_doubles<N, B, true, true>(maxruns, maxsf, maxsi, maxcell)
-                       : pdht::terms_lds_doubles<N, B, true, false>(maxruns, maxsf, maxsi, maxcell));
-  });
-  return bytes;
-}
+using pdht::for_kind;
 
 // Set-up, once per problem: the records of 1-D rules (PdhTerms::tdata) from the point arrays resident in HBM
 __global__ void __launch_bounds__(PDH_WAVE) k_terms_gather(const PdhDev P, const PdhTerms T, double *__restrict__ out, const int n_owned)
@@ -64,8 +20,6 @@ extern "C" hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T
   hipLaunchKernelGGL(k_terms_gather, dim3((unsigned)count), dim3(PDH_WAVE), 0, stream, *P, *T, out, count);
   return hipGetLastError();
 }
-// doubles of a polytope's record of 1-D rules
-extern "C" int pdh_terms_task_doubles(int maxsf, int maxcell, int pm) { return pdht::terms_task_doubles(maxsf, maxcell, pm); }
 
 extern "C" hipError_t pdh_launch_terms(const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream)
 {

@@ -1,5 +1,6 @@
 // pdh_tiled.hip — instantiations and launcher of the tiled kernels (pdh_tiled.h): 3-D, N1D = degree + 1 = 5 .. 8.
 #include "pdh_tiled.h"
+#include "pdh_launch.h"
 
 template <int N1D>
 static hipError_t launch_n1d(int which, const PdhDev *P, int count, int ntile, hipStream_t stream)
@@ -55,5 +56,3 @@ extern "C" hipError_t pdh_launch_tiled(int dim, int n1d, int which, const PdhDev
       return hipErrorInvalidValue;
     }
 }
-
-extern "C" int pdh_tiled_has_kind(int dim, int n1d, int n) { return dim == 3 && n1d >= 5 && n1d <= 8 && n > 64; }

@@ -112,7 +112,7 @@ def test_kernel_selection_on_box_meshes(mesh, basis, p):
 @pytest.mark.parametrize("off,terms,rows_p3", am.OFFSET_BOUNDARY)
 def test_offset_boundary_of_the_fast_path(off, terms, rows_p3):
     """The 4^3-cell mesh of 2^3 blocks, cells of 0.25, moved by `off` in every axis: the offset at which AUTO silently leaves the
-    term kernels (geometry_rounding, pdh_capi.cpp) is pinned here - between |x| / h = 1200 and 1600 for FE_AggloDGP(3) / FE_DGQ(3)
+    term kernels (geometry_rounding, pdh_plan.cpp) is pinned here - between |x| / h = 1200 and 1600 for FE_AggloDGP(3) / FE_DGQ(3)
     (lower elements: not monotone in the offset, e.g. FE_DGQ(2) refused at 1200 and taken at 1600 - rounding of the points decides)."""
     for basis, p in (("dgp", 3), ("dgq", 3)):
         fe = _fe(basis, 3, p)

@@ -1428,7 +1428,7 @@ def _merge_stats_and_values(kw, mode):
                                                    ("graded", False, "dr")])
 def test_term_kernels_merge_cells_and_sub_faces_that_form_tensor_grids(basis, p, shape, diag_first, vname):
     """The term kernels sum over cells and sub-faces; those that form tensor grids are merged into ONE with composite 1-D rules
-    (csrc/pdh_capi.cpp: merge_terms_of_slot).  Shapes that exercise the analysis: blocks of 3^3 cells (three intervals per axis: sub-grids of
+    (csrc/pdh_plan.cpp: merge_terms_of_slot).  Shapes that exercise the analysis: blocks of 3^3 cells (three intervals per axis: sub-grids of
     2 + 1), slabs of 4 x 2 x 1 cells (different counts per axis, composite rules of 8 and 4 and 2 points... per the element's rule), and
     METIS-like grown agglomerates with PDH_TERMS_MERGE=2 (every polytope a mix of merged sub-grids, merged planes and single cells /
     sub-faces - the rule of build_terms_tables would leave them as given), and 2^3-cell blocks of a GRADED Cartesian grid (vertices

@@ -1,9 +1,10 @@
-// ASan smoke of pdh_check_problem (host-side validation/packing of the C ABI) on flattened problems.
+// ASan / UBSan smoke of the planner of the C ABI (pdh_plan.cpp: validation, packing, choice of the row kernel) on flattened problems.
 #include "../../polydeal_amd/csrc/host/polydeal_host.h"
 #include <cstdio>
 using namespace polydeal_hip;
 extern "C" int pdh_check_problem(const pdh_problem *, int32_t, int32_t, int64_t *);
 extern "C" int pdh_check_rows(const pdh_problem *, int32_t, int32_t);
+extern "C" int pdh_check_terms(const pdh_problem *, int32_t, int32_t, int64_t *);
 extern "C" int pdh_check_exchange(const pdh_problem *, int32_t, int32_t, int, int64_t *, int64_t *);
 int main()
 {
@@ -37,6 +38,13 @@ int main()
           return 1;
         if (dim == 3)
           {
+            // the term kernels: block agglomerates of Cartesian cells with tensor rules take them, through the kernels' own LDS
+            // gate - the LDS of a workgroup is positive and within the 40 KB cap
+            int64_t ts[5] = {0, 0, 0, 0, 0}, ts2[5] = {0, 0, 0, 0, 0};
+            const int rt = pdh_check_terms(&F.c, 0, F.c.n_rows, ts), rt2 = pdh_check_terms(&F.c, (nA / 3) * n, (2 * nA / 3) * n, ts2);
+            std::printf("  term kernel applies: %d %d, LDS bytes %lld %lld\n", rt, rt2, (long long)ts[4], (long long)ts2[4]);
+            if (rt != 1 || rt2 != 1 || ts[4] <= 0 || ts[4] > 40 * 1024 || ts2[4] <= 0 || ts2[4] > 40 * 1024)
+              return 1;
             FlatProblem L;
             std::vector<int> splits = {0, (nA / 2) * n, nA * n};
             ah.flatten_local(SipVariant::poisson_example(fe), L, 0, (nA / 2) * n, true, true, nullptr, &splits);
