@@ -9,7 +9,9 @@
 // `poisson --bench [dim refine degree]` keeps the device-resident timing of BASELINE.json configs[1] (2-D, 4096 polytopes).
 // `poisson --device-solve [mesh]` solves on the GPU instead (pdh_setup_preconditioner(BLOCK_JACOBI) + pdh_solve_cg on the resident
 // matrix), after the case of the reference's test/polydeal/poisson.cc, whose printed line "L2 error:0.00647702" it reproduces.
-// Usage: poisson [--device-solve] [path/to/t3.msh]
+// `--chebyshev <degree>` after it preconditions that solve with the Chebyshev polynomial of that degree over block Jacobi
+// (pdh_setup_chebyshev: smoothing range 20, 20 CG steps for the eigenvalue estimate - the reference's multigrid smoother settings).
+// Usage: poisson [--device-solve [--chebyshev <degree>]] [path/to/t3.msh]
 #include "../polydeal_amd/csrc/host/polydeal_host.h"
 #include "host_solver.h"
 
@@ -36,13 +38,17 @@ std::string find_mesh(int argc, char **argv)
 int bench(int argc, char **argv); // device-resident timing (below)
 int reference_case();             // test/polydeal/poisson.cc, solved on the device (below)
 
-// preconditioned CG on the resident matrix: block Jacobi, the stop rule of example_solver::solve_cg
+int chebyshev_degree = 0; // --chebyshev: 0 = plain block Jacobi
+
+// preconditioned CG on the resident matrix: block Jacobi or Chebyshev over it, the stop rule of example_solver::solve_cg
 int device_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<double> &x)
 {
   x.assign(rhs.size(), 0.0);
   const pdh_cg_control control = {20000, 1e-13, 0.0};
   pdh_cg_result res;
-  if (pdh_setup_preconditioner(ctx, PDH_PREC_BLOCK_JACOBI) != PDH_OK || pdh_solve_cg(ctx, &control, rhs.data(), x.data(), &res) != PDH_OK)
+  const pdh_chebyshev_control cheb = {PDH_PREC_BLOCK_JACOBI, chebyshev_degree, 20.0, 20, 0.0};
+  const int rc = chebyshev_degree > 0 ? pdh_setup_chebyshev(ctx, &cheb, nullptr) : pdh_setup_preconditioner(ctx, PDH_PREC_BLOCK_JACOBI);
+  if (rc != PDH_OK || pdh_solve_cg(ctx, &control, rhs.data(), x.data(), &res) != PDH_OK)
     {
       std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
       return -1;
@@ -60,6 +66,17 @@ int main(int argc, char **argv)
     {
       --argc;
       ++argv;
+      if (argc > 1 && std::strcmp(argv[1], "--chebyshev") == 0)
+        {
+          chebyshev_degree = argc > 2 ? std::atoi(argv[2]) : 0;
+          if (chebyshev_degree < 1)
+            {
+              std::fprintf(stderr, "--chebyshev needs a degree >= 1\n");
+              return 1;
+            }
+          argc -= 2;
+          argv += 2;
+        }
       if (reference_case() != 0)
         return 1;
     }

@@ -371,6 +371,44 @@ typedef struct pdh_cg_result
 int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *control, const double *b, double *x, pdh_cg_result *result);
 int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *control, const double *d_b, double *d_x, pdh_cg_result *result);
 
+/* Chebyshev smoother / preconditioner over point or block Jacobi (reference: PreconditionChebyshev as the multigrid smoother of
+ * examples/simplex_agglomerated_multigrid.cc:410-470 - degree 5, smoothing range 20, 20 CG steps for the eigenvalue estimate).  With P
+ * the inner preconditioner and `est` the largest Ritz value of P^-1 A:
+ *   lambda_hi = 1.2 est, lambda_lo = lambda_hi / smoothing_range, theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta,
+ *   rho_0 = 1 / sigma;   r_0 = b - A x_0,  d_0 = (1 / theta) P^-1 r_0,  x_1 = x_0 + d_0;   for k = 1 .. degree - 1:
+ *   r_k = r_(k-1) - A d_(k-1),  rho_k = 1 / (2 sigma - rho_(k-1)),  d_k = rho_k rho_(k-1) d_(k-1) + (2 rho_k / delta) P^-1 r_k,
+ *   x_(k+1) = x_k + d_k.
+ * One application is degree - 1 products with A (one more from a non-zero start) and degree fused updates queued back to back: the
+ * coefficients are computed on the host at the set-up, nothing is synchronised inside.  est comes from eig_cg_n_iterations steps of
+ * P-preconditioned CG on A x = b0 from x = 0 on the device, b0[i] = ((2654435761 i) mod 2^32) / 2^32 - 1/2: the largest eigenvalue
+ * of the Lanczos tridiagonal of its alpha_j, beta_j (T_jj = 1 / alpha_j + beta_(j-1) / alpha_(j-1), T_(j,j+1) = sqrt(beta_j) /
+ * alpha_j; fewer steps if the residual reaches zero).  max_eigenvalue > 0 is taken as est instead and no CG runs.
+ * pdh_setup_chebyshev builds the inner preconditioner (failures as for pdh_setup_preconditioner), estimates, and makes
+ * PDH_PREC_CHEBYSHEV the preconditioner of pdh_precondition_device (z = the application to r from a zero start) and pdh_solve_cg*.
+ * PDH_EINVAL: degree < 1, smoothing_range <= 1, inner not one of the two, eig_cg_n_iterations outside 1 .. 256 while it is needed.
+ * Needs a context that owns all rows with PDH_EXCHANGE_NONE (PDH_EUNSUPPORTED), like pdh_solve_cg.  pdh_setup_preconditioner does
+ * not take PDH_PREC_CHEBYSHEV (PDH_EINVAL).  pdh_chebyshev_step_device is the smoother: one application to b from the x given
+ * (zero_initial_guess != 0: x is not read), device pointers [n_rows], asynchronous on pdh_stream(); b and x must not overlap.    */
+#define PDH_PREC_CHEBYSHEV 3
+typedef struct pdh_chebyshev_control
+{
+  int32_t inner;               /* PDH_PREC_JACOBI | PDH_PREC_BLOCK_JACOBI */
+  int32_t degree;              /* >= 1 */
+  double smoothing_range;      /* > 1 */
+  int32_t eig_cg_n_iterations; /* 1..256, unused when max_eigenvalue > 0 */
+  double max_eigenvalue;       /* > 0: used as `est` */
+} pdh_chebyshev_control;
+typedef struct pdh_chebyshev_info
+{
+  double estimate, lambda_lo, lambda_hi;
+  int32_t cg_iterations, degree, inner;
+} pdh_chebyshev_info;
+int pdh_setup_chebyshev(pdh_ctx *ctx, const pdh_chebyshev_control *control, pdh_chebyshev_info *info /* may be NULL */);
+int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double *d_x, int zero_initial_guess);
+/* Host-only: smallest and largest eigenvalue of the symmetric tridiagonal matrix with diagonal diag [k] and off-diagonal
+ * offdiag [k-1] (not read for k = 1), 1 <= k <= 256, by bisection on Sturm counts (a few ulp of the largest |eigenvalue|). */
+int pdh_tridiagonal_eigenvalues(int k, const double *diag, const double *offdiag, double *lo, double *hi);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

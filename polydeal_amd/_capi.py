@@ -18,7 +18,7 @@ PDH_BASIS_DGQ = 0
 PDH_BASIS_AGGLODGP = 1
 PDH_OK = 0
 PDH_EINVAL, PDH_EUNSUPPORTED, PDH_EDEVICE, PDH_ESTATE, PDH_ENOCONV = -1, -2, -3, -4, -5
-PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI = 0, 1, 2
+PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI, PDH_PREC_CHEBYSHEV = 0, 1, 2, 3
 _PREC = {"none": PDH_PREC_NONE, "jacobi": PDH_PREC_JACOBI, "block_jacobi": PDH_PREC_BLOCK_JACOBI}
 CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
@@ -35,6 +35,16 @@ class pdh_cg_control(C.Structure):
 
 class pdh_cg_result(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("residual0", C.c_double), ("residual", C.c_double)]
+
+
+class pdh_chebyshev_control(C.Structure):
+    _fields_ = [("inner", C.c_int32), ("degree", C.c_int32), ("smoothing_range", C.c_double), ("eig_cg_n_iterations", C.c_int32),
+                ("max_eigenvalue", C.c_double)]
+
+
+class pdh_chebyshev_info(C.Structure):
+    _fields_ = [("estimate", C.c_double), ("lambda_lo", C.c_double), ("lambda_hi", C.c_double), ("cg_iterations", C.c_int32),
+                ("degree", C.c_int32), ("inner", C.c_int32)]
 
 
 class pdh_problem(C.Structure):
@@ -63,6 +73,7 @@ EXPORTS = [
     "pdh_assemble_rhs_device", "pdh_evaluate_device", "pdh_shape_values_device",
     "pdh_global_error", "pdh_global_error_device", "pdh_rows_kernel_in_use", "pdh_check_terms", "pdh_terms_merge_stats", "pdh_set_problem_cartesian",
     "pdh_vmult", "pdh_vmult_device", "pdh_setup_preconditioner", "pdh_precondition_device", "pdh_solve_cg", "pdh_solve_cg_device",
+    "pdh_setup_chebyshev", "pdh_chebyshev_step_device", "pdh_tridiagonal_eigenvalues",
 ]
 
 _lib = None
@@ -139,7 +150,24 @@ def _bind(lib):
     lib.pdh_precondition_device.argtypes = [C.c_void_p] * 3
     lib.pdh_solve_cg.argtypes = [C.c_void_p, P(pdh_cg_control), C.c_void_p, C.c_void_p, P(pdh_cg_result)]
     lib.pdh_solve_cg_device.argtypes = [C.c_void_p, P(pdh_cg_control), C.c_void_p, C.c_void_p, P(pdh_cg_result)]
+    lib.pdh_setup_chebyshev.argtypes = [C.c_void_p, P(pdh_chebyshev_control), P(pdh_chebyshev_info)]
+    lib.pdh_chebyshev_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pdh_tridiagonal_eigenvalues.argtypes = [C.c_int, C.c_void_p, C.c_void_p, P(C.c_double), P(C.c_double)]
     return real
+
+
+def tridiagonal_eigenvalues(diag, offdiag):
+    """(smallest, largest) eigenvalue of the symmetric tridiagonal matrix (diag [k], offdiag [k-1]); host only, no GPU."""
+    lib = load_library()
+    d = np.ascontiguousarray(diag, dtype=np.float64)
+    e = np.ascontiguousarray(offdiag, dtype=np.float64)
+    if d.ndim != 1 or e.shape != (max(len(d) - 1, 0),):
+        raise ValueError("diag [k] and offdiag [k-1]")
+    lo, hi = C.c_double(), C.c_double()
+    rc = lib.pdh_tridiagonal_eigenvalues(len(d), d.ctypes.data, e.ctypes.data if len(e) else None, C.byref(lo), C.byref(hi))
+    if rc != PDH_OK:
+        raise PdhError(rc, lib.pdh_last_error(None).decode())
+    return lo.value, hi.value
 
 
 def load_library(path=None):
@@ -358,6 +386,48 @@ class Context:
 
     def precondition_device(self, d_r, d_z):
         self._chk(self.lib.pdh_precondition_device(self.h, C.c_void_p(d_r), C.c_void_p(d_z)))
+
+    def setup_chebyshev(self, inner="block_jacobi", degree=5, smoothing_range=20.0, eig_cg_n_iterations=20, max_eigenvalue=0.0):
+        """Chebyshev polynomial of `degree` in P^-1 A over the inner preconditioner 'jacobi' | 'block_jacobi' (pdh_setup_chebyshev); it
+        becomes the preconditioner of precondition_device and solve_cg*.  Returns {estimate, lambda_lo, lambda_hi, cg_iterations,
+        degree, inner}."""
+        ctl = pdh_chebyshev_control(_PREC[inner] if isinstance(inner, str) else int(inner), int(degree), float(smoothing_range),
+                                    int(eig_cg_n_iterations), float(max_eigenvalue))
+        info = pdh_chebyshev_info()
+        self._chk(self.lib.pdh_setup_chebyshev(self.h, C.byref(ctl), C.byref(info)))
+        return {"estimate": float(info.estimate), "lambda_lo": float(info.lambda_lo), "lambda_hi": float(info.lambda_hi),
+                "cg_iterations": int(info.cg_iterations), "degree": int(info.degree),
+                "inner": {v: k for k, v in _PREC.items()}[int(info.inner)]}
+
+    def chebyshev_step_device(self, d_b, d_x, zero_initial_guess=False):
+        """One application of the smoother to b from the x in d_x (device pointers as ints); asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_chebyshev_step_device(self.h, C.c_void_p(d_b), C.c_void_p(d_x), int(bool(zero_initial_guess))))
+
+    def chebyshev_step(self, b, x=None):
+        """One application of the smoother to b from x (None: from zero); host arrays, returns the new x."""
+        bb = np.ascontiguousarray(b, dtype=np.float64)
+        xx = np.zeros(self.n_rows) if x is None else np.array(x, dtype=np.float64, copy=True)
+        if bb.shape != (self.n_rows,) or xx.shape != (self.n_rows,):
+            raise ValueError("b and x must have n_rows = %d entries" % self.n_rows)
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipFree.argtypes = [C.c_void_p]
+        d_b, d_x = C.c_void_p(), C.c_void_p()
+        try:
+            if hip.hipMalloc(C.byref(d_b), max(bb.nbytes, 8)) != 0 or hip.hipMalloc(C.byref(d_x), max(xx.nbytes, 8)) != 0:
+                raise PdhError(PDH_EDEVICE, "chebyshev_step: out of device memory")
+            if hip.hipMemcpy(d_b, bb.ctypes.data, bb.nbytes, 1) != 0 or hip.hipMemcpy(d_x, xx.ctypes.data, xx.nbytes, 1) != 0:
+                raise PdhError(PDH_EDEVICE, "chebyshev_step: copy to the device failed")
+            self.chebyshev_step_device(d_b.value, d_x.value, x is None)
+            self.synchronize()
+            if hip.hipMemcpy(xx.ctypes.data, d_x, xx.nbytes, 2) != 0:
+                raise PdhError(PDH_EDEVICE, "chebyshev_step: copy from the device failed")
+        finally:
+            for p in (d_b, d_x):
+                if p.value:
+                    hip.hipFree(p)
+        return xx
 
     def _cg(self, fn, b, x, rel_tol, abs_tol, max_iter, on_noconv):
         ctl = pdh_cg_control(CG_MAX_ITER if max_iter is None else int(max_iter), float(rel_tol), float(abs_tol))

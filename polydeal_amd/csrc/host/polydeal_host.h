@@ -1668,6 +1668,19 @@ inline std::array<double, 2> compute_global_error(pdh_ctx *ctx, const FlatProble
     throw std::runtime_error(std::string("pdh_global_error: ") + pdh_last_error(ctx));
   return {std::sqrt(sums[0]), want_h1 ? std::sqrt(sums[1]) : 0.0};
 }
+
+// PreconditionChebyshev::AdditionalData + initialize (reference examples/simplex_agglomerated_multigrid.cc:410-470: degree 5,
+// smoothing_range 20, eig_cg_n_iterations 20) on the matrix resident in `ctx`: pdh_setup_chebyshev with the reference's defaults.
+// Afterwards pdh_solve_cg* and pdh_precondition_device use the polynomial, pdh_chebyshev_step_device is the smoother.
+inline pdh_chebyshev_info setup_chebyshev(pdh_ctx *ctx, int inner = PDH_PREC_BLOCK_JACOBI, int degree = 5, double smoothing_range = 20.0,
+                                          int eig_cg_n_iterations = 20, double max_eigenvalue = 0.0)
+{
+  const pdh_chebyshev_control control = {inner, degree, smoothing_range, eig_cg_n_iterations, max_eigenvalue};
+  pdh_chebyshev_info info;
+  if (pdh_setup_chebyshev(ctx, &control, &info) != PDH_OK)
+    throw std::runtime_error(std::string("pdh_setup_chebyshev: ") + pdh_last_error(ctx));
+  return info;
+}
 } // namespace PolyUtilsHIP
 
 namespace Utils

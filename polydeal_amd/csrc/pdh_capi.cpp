@@ -113,9 +113,13 @@ struct pdh_ctx
   uint64_t values_gen = 0, prec_gen = 0;
   int prec_kind = PDH_PREC_NONE;
   bool prec_ok = true;
-  enum { SOL_DINV, SOL_FLAG, SOL_R, SOL_Z, SOL_P, SOL_Q, SOL_PART, SOL_SCAL, SOL_N };
+  enum { SOL_DINV, SOL_FLAG, SOL_R, SOL_Z, SOL_P, SOL_Q, SOL_PART, SOL_SCAL, SOL_CHEB_D, SOL_CHEB_R, SOL_N };
   Scratch sol[SOL_N];
-  double *pinned = nullptr;
+  double *pinned = nullptr; // [PDH_CG_NSCALARS]
+  // PDH_PREC_CHEBYSHEV (pdh_setup_chebyshev): the inner kind whose inverse lies in SOL_DINV and, per step k, the factors of d_(k-1)
+  // and of P^-1 r_k in d_k (step 0: unused and 1 / theta)
+  int cheb_inner = PDH_PREC_NONE;
+  std::vector<double> cheb_c1, cheb_c2;
   template <class T>
   T *sol_get(int i, size_t count)
   {
@@ -1646,6 +1650,28 @@ static int prec_checks(pdh_ctx *ctx)
   return PDH_OK;
 }
 
+// One application of the Chebyshev polynomial to b, queued on the stream: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b,
+// x not read).  d, r and q are the context's own vectors - never CG's residual.  rcg / part: see pdh_launch_cheb_update.
+static int cheb_apply(pdh_ctx *ctx, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part)
+{
+  double *d = static_cast<double *>(ctx->sol[pdh_ctx::SOL_CHEB_D].p), *r = static_cast<double *>(ctx->sol[pdh_ctx::SOL_CHEB_R].p);
+  double *q = static_cast<double *>(ctx->sol[pdh_ctx::SOL_Q].p);
+  const double *dinv = static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p);
+  const int m = (int)ctx->cheb_c2.size();
+  if (!d || !r || !q || !dinv || m < 1)
+    return fail(ctx, PDH_ESTATE, "the Chebyshev preconditioner is not set up");
+  if (!zero)
+    PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, ctx->stream));
+  for (int k = 0; k < m; ++k)
+    {
+      if (k > 0)
+        PDH_HIP(ctx, pdh_launch_vmult(&A, d, q, nullptr, ctx->stream));
+      PDH_HIP(ctx, pdh_launch_cheb_update(&A, k == 0, ctx->cheb_inner, dinv, b, (k == 0 && zero) ? nullptr : q, d, r, x, ctx->cheb_c1[k],
+                                          ctx->cheb_c2[k], k == 0 && zero, k == m - 1 ? rcg : nullptr, part, ctx->stream));
+    }
+  return PDH_OK;
+}
+
 extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *d_z)
 {
   if (!ctx)
@@ -1657,6 +1683,8 @@ extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *
   PDH_TRY(prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   const PdhSolveArgs A = solve_args(ctx);
+  if (ctx->prec_kind == PDH_PREC_CHEBYSHEV)
+    return cheb_apply(ctx, A, d_r, d_z, true, nullptr, nullptr);
   PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_APPLY, ctx->prec_kind, static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p),
                                     nullptr, nullptr, nullptr, nullptr, const_cast<double *>(d_r), d_z, nullptr, nullptr, ctx->stream));
   return PDH_OK;
@@ -1690,17 +1718,22 @@ extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const 
   double *p = ctx->sol_get<double>(pdh_ctx::SOL_P, N), *q = ctx->sol_get<double>(pdh_ctx::SOL_Q, N);
   double *part = ctx->sol_get<double>(pdh_ctx::SOL_PART, (size_t)PDH_CG_NPART * ctx->n_owned);
   double *scal = ctx->sol_get<double>(pdh_ctx::SOL_SCAL, PDH_CG_NSCALARS);
-  if (!ctx->pinned && hipHostMalloc((void **)&ctx->pinned, 2 * sizeof(double), hipHostMallocDefault) != hipSuccess)
+  if (!ctx->pinned && hipHostMalloc((void **)&ctx->pinned, PDH_CG_NSCALARS * sizeof(double), hipHostMallocDefault) != hipSuccess)
     ctx->pinned = nullptr;
   if (!r || !z || !p || !q || !part || !scal || !ctx->pinned)
     return fail(ctx, PDH_EDEVICE, "pdh_solve_cg: out of device memory");
   const double *dinv = static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p);
-  const int kind = ctx->prec_kind;
+  // Chebyshev: the fused update leaves z alone (kind none) and the chain z = p(P^-1 A) P^-1 r follows it; its last step writes the
+  // partials of r^T z
+  const bool cheb = ctx->prec_kind == PDH_PREC_CHEBYSHEV;
+  const int kind = cheb ? PDH_PREC_NONE : ctx->prec_kind;
   const PdhSolveArgs A = solve_args(ctx);
   hipStream_t st = ctx->stream;
   // r = b - A x0, z = P^-1 r, p = z
   PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, q, nullptr, st));
   PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, d_b, q, nullptr, nullptr, r, z, scal, part, st));
+  if (cheb)
+    PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
   PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 0, scal, st));
   PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
   PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + PDH_CG_RR, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1716,6 +1749,8 @@ extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const 
       PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * ctx->n_owned, st));
       PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 1, scal, st));
       PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, d_x, r, z, scal, part, st));
+      if (cheb)
+        PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
       PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 2, scal, st));
       PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
       PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + PDH_CG_RR, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1757,4 +1792,164 @@ extern "C" int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *c, const double 
   if (rc == PDH_ENOCONV)
     ctx->err = msg;
   return rc;
+}
+
+// ---- Chebyshev smoother / preconditioner (include/polydeal_hip.h: pdh_setup_chebyshev) ----------------------------------------------
+static int all_rows_checks(pdh_ctx *ctx, const char *who)
+{
+  if (ctx->problem_ghost)
+    return fail(ctx, PDH_EUNSUPPORTED, std::string(who) + ": the problem was set in PDH_EXCHANGE_GHOST mode; it needs a context that owns "
+                                                          "all rows with PDH_EXCHANGE_NONE");
+  if (ctx->n_rows_owned != ctx->n_rows_total)
+    return fail(ctx, PDH_EUNSUPPORTED, std::string(who) + ": the context owns rows " + std::to_string(ctx->n_rows_owned) + " of " +
+                                         std::to_string(ctx->n_rows_total) + "; it needs all rows in one context");
+  if ((int64_t)ctx->max_row_len * (int64_t)sizeof(double) > PDH_VMULT_LDS_CAP)
+    return fail(ctx, PDH_EUNSUPPORTED, "a row has more than 8192 entries (the column set of a polytope must fit 64 KB of LDS)");
+  return PDH_OK;
+}
+
+// Largest Ritz value of P^-1 A after k steps of P-preconditioned CG on A x = b0 from x = 0 (P = the inner preconditioner, set up and
+// current): the launches of pdh_solve_cg_device, but alpha_j, beta_j and ||r||^2 come back every step - a path of its own, the
+// solver's loop keeps reading 8 bytes.  steps: CG steps that entered the Lanczos matrix.
+static int cheb_estimate(pdh_ctx *ctx, int kind, int k, double *est, int *steps)
+{
+  const int64_t N = ctx->n_rows_owned;
+  double *r = ctx->sol_get<double>(pdh_ctx::SOL_R, N), *z = ctx->sol_get<double>(pdh_ctx::SOL_Z, N);
+  double *p = ctx->sol_get<double>(pdh_ctx::SOL_P, N), *q = ctx->sol_get<double>(pdh_ctx::SOL_Q, N);
+  double *part = ctx->sol_get<double>(pdh_ctx::SOL_PART, (size_t)PDH_CG_NPART * ctx->n_owned);
+  double *scal = ctx->sol_get<double>(pdh_ctx::SOL_SCAL, PDH_CG_NSCALARS);
+  double *d_b = static_cast<double *>(ctx->scratch_get(0, std::max<int64_t>(N, 1) * sizeof(double)));
+  double *d_x = static_cast<double *>(ctx->scratch_get(1, std::max<int64_t>(N, 1) * sizeof(double)));
+  if (!ctx->pinned && hipHostMalloc((void **)&ctx->pinned, PDH_CG_NSCALARS * sizeof(double), hipHostMallocDefault) != hipSuccess)
+    ctx->pinned = nullptr;
+  if (!r || !z || !p || !q || !part || !scal || !d_b || !d_x || !ctx->pinned)
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_chebyshev: out of device memory");
+  std::vector<double> b0((size_t)N);
+  for (int64_t i = 0; i < N; ++i)
+    b0[(size_t)i] = (double)(uint32_t)(2654435761ull * (uint64_t)i) / 4294967296.0 - 0.5;
+  hipStream_t st = ctx->stream;
+  const double *dinv = static_cast<const double *>(ctx->sol[pdh_ctx::SOL_DINV].p);
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, hipMemcpyAsync(d_b, b0.data(), N * sizeof(double), hipMemcpyHostToDevice, st));
+  PDH_HIP(ctx, hipMemsetAsync(d_x, 0, N * sizeof(double), st));
+  PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, q, nullptr, st));
+  PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, d_b, q, nullptr, nullptr, r, z, scal, part, st));
+  PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 0, scal, st));
+  PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
+  PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal, PDH_CG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st));
+  PDH_HIP(ctx, hipStreamSynchronize(st));
+  double rr = ctx->pinned[PDH_CG_RR];
+  std::vector<double> alpha, beta;
+  for (int it = 0; it < k && rr > 0.0; ++it)
+    {
+      PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * ctx->n_owned, st));
+      PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 1, scal, st));
+      PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, d_x, r, z, scal, part, st));
+      PDH_HIP(ctx, pdh_launch_cg_finalise(part, ctx->n_owned, 2, scal, st));
+      PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
+      PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal, PDH_CG_NSCALARS * sizeof(double), hipMemcpyDeviceToHost, st));
+      PDH_HIP(ctx, hipStreamSynchronize(st));
+      const double a = ctx->pinned[PDH_CG_ALPHA], b = ctx->pinned[PDH_CG_BETA];
+      if (!(a > 0.0) || !std::isfinite(a) || !(b >= 0.0) || !std::isfinite(b))
+        break; // p^T A p <= 0 or a breakdown: the steps so far
+      alpha.push_back(a);
+      beta.push_back(b);
+      rr = ctx->pinned[PDH_CG_RR];
+    }
+  const int m = (int)alpha.size();
+  if (m < 1)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: the eigenvalue estimate took no CG step (no rows, or the matrix is not positive "
+                                 "definite on the test vector)");
+  std::vector<double> dg((size_t)m), od((size_t)std::max(m - 1, 1));
+  for (int j = 0; j < m; ++j)
+    {
+      dg[j] = j == 0 ? 1.0 / alpha[j] : 1.0 / alpha[j] + beta[j - 1] / alpha[j - 1];
+      if (j + 1 < m)
+        od[j] = std::sqrt(beta[j]) / alpha[j];
+    }
+  double lo = 0.0, hi = 0.0;
+  if (pdh_tridiagonal_eigenvalues(m, dg.data(), od.data(), &lo, &hi) != PDH_OK)
+    return fail(ctx, PDH_EINVAL, std::string("pdh_setup_chebyshev: ") + pdh_last_error(nullptr));
+  *est = hi;
+  *steps = m;
+  return PDH_OK;
+}
+
+extern "C" int pdh_setup_chebyshev(pdh_ctx *ctx, const pdh_chebyshev_control *c, pdh_chebyshev_info *info)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_setup_chebyshev called before pdh_set_problem");
+  if (!c)
+    return fail(ctx, PDH_EINVAL, "control is required");
+  if (c->inner != PDH_PREC_JACOBI && c->inner != PDH_PREC_BLOCK_JACOBI)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: inner must be PDH_PREC_JACOBI or PDH_PREC_BLOCK_JACOBI");
+  if (c->degree < 1)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: degree must be at least 1");
+  if (!(c->smoothing_range > 1.0) || !std::isfinite(c->smoothing_range))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: smoothing_range must be finite and greater than 1");
+  if (std::isnan(c->max_eigenvalue) || std::isinf(c->max_eigenvalue))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: max_eigenvalue is not finite");
+  const bool given = c->max_eigenvalue > 0.0;
+  if (!given && (c->eig_cg_n_iterations < 1 || c->eig_cg_n_iterations > 256))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: eig_cg_n_iterations must be 1 .. 256 (or give max_eigenvalue > 0)");
+  PDH_TRY(all_rows_checks(ctx, "pdh_setup_chebyshev"));
+  PDH_TRY(pdh_setup_preconditioner(ctx, c->inner)); // the inner inverse; prec_kind = inner for the estimate
+  ctx->prec_ok = false;                             // until the whole set-up has succeeded
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  double est = c->max_eigenvalue;
+  int steps = 0;
+  if (!given)
+    PDH_TRY(cheb_estimate(ctx, c->inner, c->eig_cg_n_iterations, &est, &steps));
+  if (!(est > 0.0) || !std::isfinite(est))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: the eigenvalue estimate " + std::to_string(est) + " is not positive");
+  const int64_t N = ctx->n_rows_owned;
+  if (!ctx->sol_get<double>(pdh_ctx::SOL_CHEB_D, N) || !ctx->sol_get<double>(pdh_ctx::SOL_CHEB_R, N) ||
+      !ctx->sol_get<double>(pdh_ctx::SOL_Q, N))
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_chebyshev: out of device memory");
+  const double hi = 1.2 * est, lo = hi / c->smoothing_range;
+  const double theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta;
+  ctx->cheb_c1.assign((size_t)c->degree, 0.0);
+  ctx->cheb_c2.assign((size_t)c->degree, 0.0);
+  ctx->cheb_c2[0] = 1 / theta;
+  double rho_old = 1 / sigma;
+  for (int k = 1; k < c->degree; ++k)
+    {
+      const double rho = 1 / (2 * sigma - rho_old);
+      ctx->cheb_c1[k] = rho * rho_old;
+      ctx->cheb_c2[k] = 2 * rho / delta;
+      rho_old = rho;
+    }
+  ctx->cheb_inner = c->inner;
+  ctx->prec_kind = PDH_PREC_CHEBYSHEV;
+  ctx->prec_gen = ctx->values_gen;
+  ctx->prec_ok = true;
+  if (info)
+    {
+      info->estimate = est;
+      info->lambda_lo = lo;
+      info->lambda_hi = hi;
+      info->cg_iterations = steps;
+      info->degree = c->degree;
+      info->inner = c->inner;
+    }
+  return PDH_OK;
+}
+
+extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double *d_x, int zero_initial_guess)
+{
+  if (!ctx)
+    return fail(nullptr, PDH_EINVAL, "ctx is NULL");
+  if (!ctx->has_problem)
+    return fail(ctx, PDH_ESTATE, "pdh_chebyshev_step_device called before pdh_set_problem");
+  if (!d_b || !d_x)
+    return fail(ctx, PDH_EINVAL, "b and x are required");
+  if (overlap(d_b, ctx->n_rows_total, d_x, ctx->n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  if (ctx->prec_kind != PDH_PREC_CHEBYSHEV)
+    return fail(ctx, PDH_ESTATE, "pdh_chebyshev_step_device: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
+  PDH_TRY(prec_checks(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  return cheb_apply(ctx, solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
 }

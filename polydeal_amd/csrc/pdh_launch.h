@@ -68,6 +68,11 @@ hipError_t pdh_launch_diag_inverse(const PdhSolveArgs *A, double *dinv, int32_t 
 // the fused vector kernel (PdhCgMode; kind = PDH_PREC_*); vectors indexed by owned row
 hipError_t pdh_launch_cg_update(const PdhSolveArgs *A, int mode, int kind, const double *dinv, const double *b, const double *q,
                                 const double *p, double *x, double *r, double *z, const double *scal, double *part, hipStream_t stream);
+// one step of the Chebyshev chain (pdh_setup_chebyshev; kind = PDH_PREC_JACOBI | PDH_PREC_BLOCK_JACOBI): r = first ? b (- q if q) : r - q,
+// d = first ? c2 P^-1 r : c1 d + c2 P^-1 r, x = (first && zero_start) ? d : x + d; rcg (may be NULL): partial of rcg^T x to PDH_PART_RZ
+hipError_t pdh_launch_cheb_update(const PdhSolveArgs *A, int first, int kind, const double *dinv, const double *b, const double *q,
+                                  double *d, double *r, double *x, double c1, double c2, int zero_start, const double *rcg, double *part,
+                                  hipStream_t stream);
 // p = z + beta p (init: p = z) over n_rows entries
 hipError_t pdh_launch_cg_direction(int64_t n_rows, int init, const double *z, double *p, const double *scal, hipStream_t stream);
 // one workgroup: partials -> scalars.  stage 0: rz, rr, bb;  1: pq, alpha;  2: rz, rr, beta

@@ -1767,3 +1767,65 @@ extern "C" int pdh_check_exchange(const pdh_problem *p, int32_t row_begin, int32
     }
   return PDH_OK;
 }
+
+// Host-only: extreme eigenvalues of a symmetric tridiagonal matrix (the Lanczos matrix of pdh_setup_chebyshev's CG steps).  Bisection
+// on the Sturm count of T - x I (number of negative pivots q_i = d_i - x - e_(i-1)^2 / q_(i-1) = number of eigenvalues below x),
+// started from the Gershgorin interval and run until the interval holds no further double.
+extern "C" int pdh_tridiagonal_eigenvalues(int k, const double *diag, const double *offdiag, double *lo, double *hi)
+{
+  g_err_noctx.clear();
+  if (k < 1 || k > 256 || !diag || (k > 1 && !offdiag) || !lo || !hi)
+    return fail(g_err_noctx, PDH_EINVAL, "pdh_tridiagonal_eigenvalues: 1 <= k <= 256, diag, offdiag (k > 1), lo and hi are required");
+  double gl = diag[0], gu = diag[0], emax = 0.0;
+  for (int i = 0; i < k; ++i)
+    {
+      const double el = i > 0 ? std::fabs(offdiag[i - 1]) : 0.0, er = i + 1 < k ? std::fabs(offdiag[i]) : 0.0;
+      if (!std::isfinite(diag[i]) || !std::isfinite(el) || !std::isfinite(er))
+        return fail(g_err_noctx, PDH_EINVAL, "pdh_tridiagonal_eigenvalues: entry " + std::to_string(i) + " is not finite");
+      gl = std::min(gl, diag[i] - el - er);
+      gu = std::max(gu, diag[i] + el + er);
+      emax = std::max(emax, er);
+    }
+  if (k == 1)
+    {
+      *lo = *hi = diag[0];
+      return PDH_OK;
+    }
+  const double norm = std::max(std::fabs(gl), std::fabs(gu));
+  const double pivmin = std::max(2.2250738585072014e-308, 2.2250738585072014e-308 * emax * emax);
+  const double pad = 2.0 * 2.220446049250313e-16 * norm * k + 2.0 * pivmin;
+  gl -= pad;
+  gu += pad;
+  auto below = [&](double x) { // number of eigenvalues < x
+    int c = 0;
+    double q = diag[0] - x;
+    if (std::fabs(q) < pivmin)
+      q = -pivmin;
+    c += q < 0.0;
+    for (int i = 1; i < k; ++i)
+      {
+        q = diag[i] - x - offdiag[i - 1] * offdiag[i - 1] / q;
+        if (std::fabs(q) < pivmin)
+          q = -pivmin;
+        c += q < 0.0;
+      }
+    return c;
+  };
+  auto kth = [&](int want) { // eigenvalue number `want` (0 = smallest): below(a) <= want < below(b) throughout
+    double a = gl, b = gu;
+    for (int it = 0; it < 2200; ++it)
+      {
+        const double m = a + 0.5 * (b - a);
+        if (!(m > a && m < b))
+          break;
+        if (below(m) <= want)
+          a = m;
+        else
+          b = m;
+      }
+    return a + 0.5 * (b - a);
+  };
+  *lo = kth(0);
+  *hi = kth(k - 1);
+  return PDH_OK;
+}

@@ -42,6 +42,8 @@ enum PdhCgPartial
   PDH_PART_BB = 3,
   PDH_CG_NPART = 4
 };
+// (the Chebyshev chain - pdh_launch_cheb_update - takes its coefficients as kernel arguments and writes only PDH_PART_RZ, on its last
+// step inside CG; it reads no scalar)
 // modes of the fused vector kernel pdh_launch_cg_update
 enum PdhCgMode
 {

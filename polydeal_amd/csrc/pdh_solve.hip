@@ -1,5 +1,6 @@
 // pdh_solve.hip — y = A x on the resident values, the point / block Jacobi preconditioners and the vector kernels of conjugate
-// gradients (C ABI: pdh_vmult*, pdh_setup_preconditioner, pdh_precondition_device, pdh_solve_cg*; layout: pdh_solve.h).
+// gradients and of the Chebyshev smoother (C ABI: pdh_vmult*, pdh_setup_preconditioner, pdh_setup_chebyshev, pdh_precondition_device,
+// pdh_chebyshev_step_device, pdh_solve_cg*; layout: pdh_solve.h).
 //
 // Every sum has a fixed order: a lane adds its terms in index order, a wave adds its 64 lanes by a butterfly, the slots' partials
 // are added by ONE workgroup in slot order (k_cg_finalise).  No atomics: the same call on the same data gives the same bits.
@@ -283,6 +284,66 @@ __global__ void __launch_bounds__(W) k_cg_update(const PdhSolveArgs A, const dou
     }
 }
 
+// One wave per owned polytope: one step of the Chebyshev chain of pdh_setup_chebyshev (same slot walk as k_cg_update),
+//   r <- FIRST ? b (- q if the start is not zero) : r - q;   z = P^-1 r;   d <- FIRST ? c2 z : c1 d + c2 z;   x <- x + d
+// (FIRST from a zero start: x <- d, x is not read).  q = A x0 (FIRST) or A d of the previous step, by k_vmult.  b and x may be the
+// same array (a slot's b is read before its x is written).  rcg (may be NULL; may be b): the slot's partial of rcg^T x goes to
+// part[PDH_PART_RZ] - the last step of an application inside CG, so that k_cg_finalise stays the one place where partials are added.
+template <bool FIRST, int KIND>
+__global__ void __launch_bounds__(W) k_cheb_update(const PdhSolveArgs A, const double *__restrict__ dinv, const double *b,
+                                                   const double *__restrict__ q, double *__restrict__ d, double *__restrict__ r, double *x,
+                                                   double c1, double c2, int zero_start, const double *rcg, double *__restrict__ part)
+{
+  __shared__ double rs[W];
+  const int s = blockIdx.x, lane = threadIdx.x, n = A.n;
+  const int64_t o = A.own_row[s];
+  double rz = 0.0;
+  for (int i0 = 0; i0 < n; i0 += W)
+    {
+      const int i = i0 + lane;
+      const bool on = i < n;
+      double ri = 0.0;
+      if (on)
+        {
+          if (FIRST)
+            ri = q ? b[o + i] - q[o + i] : b[o + i];
+          else
+            ri = r[o + i] - q[o + i];
+        }
+      double zi = 0.0;
+      if (KIND == PREC_BLOCK)
+        { // n <= 64: one pass; row j of the symmetric inverse read whole by the wave, as in k_cg_update
+          rs[lane] = ri;
+          __syncthreads();
+          const double *__restrict__ D = dinv + (int64_t)s * n * n + i;
+          if (on)
+            {
+#pragma unroll 8
+              for (int j = 0; j < n; ++j)
+                zi += __builtin_nontemporal_load(D + (int64_t)j * n) * rs[j];
+            }
+        }
+      else
+        zi = on ? dinv[o + i] * ri : 0.0;
+      if (on)
+        {
+          const double di = FIRST ? c2 * zi : c1 * d[o + i] + c2 * zi;
+          const double xi = (FIRST && zero_start) ? di : x[o + i] + di;
+          r[o + i] = ri;
+          d[o + i] = di;
+          x[o + i] = xi;
+          if (rcg)
+            rz += rcg[o + i] * xi;
+        }
+    }
+  if (rcg)
+    {
+      rz = wave_sum(rz);
+      if (lane == 0)
+        part[PDH_PART_RZ * (int64_t)A.n_owned + s] = rz;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_cg_direction(int64_t N, int init, const double *__restrict__ z, double *__restrict__ p,
                                                       const double *__restrict__ scal)
 {
@@ -419,5 +480,31 @@ extern "C" hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, in
   if (stage < 0 || stage > 2)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_cg_finalise, dim3(1), dim3(256), 0, stream, part, n_owned, stage, scal);
+  return hipGetLastError();
+}
+
+template <bool FIRST>
+static void launch_cheb(const PdhSolveArgs *A, int kind, const double *dinv, const double *b, const double *q, double *d, double *r,
+                        double *x, double c1, double c2, int zero_start, const double *rcg, double *part, hipStream_t stream)
+{
+  const dim3 g(A->n_owned), blk(W);
+  if (kind == PREC_BLOCK)
+    hipLaunchKernelGGL((k_cheb_update<FIRST, PREC_BLOCK>), g, blk, 0, stream, *A, dinv, b, q, d, r, x, c1, c2, zero_start, rcg, part);
+  else
+    hipLaunchKernelGGL((k_cheb_update<FIRST, PREC_JACOBI>), g, blk, 0, stream, *A, dinv, b, q, d, r, x, c1, c2, zero_start, rcg, part);
+}
+
+extern "C" hipError_t pdh_launch_cheb_update(const PdhSolveArgs *A, int first, int kind, const double *dinv, const double *b,
+                                             const double *q, double *d, double *r, double *x, double c1, double c2, int zero_start,
+                                             const double *rcg, double *part, hipStream_t stream)
+{
+  if (A->n_owned <= 0)
+    return hipSuccess;
+  if ((kind != PREC_BLOCK && kind != PREC_JACOBI) || (kind == PREC_BLOCK && A->n > W) || (!first && !q) || (rcg && !part))
+    return hipErrorInvalidValue;
+  if (first)
+    launch_cheb<true>(A, kind, dinv, b, q, d, r, x, c1, c2, zero_start, rcg, part, stream);
+  else
+    launch_cheb<false>(A, kind, dinv, b, q, d, r, x, c1, c2, zero_start, rcg, part, stream);
   return hipGetLastError();
 }

@@ -1,11 +1,13 @@
 // ASan / UBSan smoke of the planner of the C ABI (pdh_plan.cpp: validation, packing, choice of the row kernel) on flattened problems.
 #include "../../polydeal_amd/csrc/host/polydeal_host.h"
+#include <cmath>
 #include <cstdio>
 using namespace polydeal_hip;
 extern "C" int pdh_check_problem(const pdh_problem *, int32_t, int32_t, int64_t *);
 extern "C" int pdh_check_rows(const pdh_problem *, int32_t, int32_t);
 extern "C" int pdh_check_terms(const pdh_problem *, int32_t, int32_t, int64_t *);
 extern "C" int pdh_check_exchange(const pdh_problem *, int32_t, int32_t, int, int64_t *, int64_t *);
+extern "C" int pdh_tridiagonal_eigenvalues(int, const double *, const double *, double *, double *);
 int main()
 {
   for (int dim = 2; dim <= 3; ++dim)
@@ -55,5 +57,23 @@ int main()
             std::printf("  local description: owned %lld, exchange send %lld recv %lld doubles\n", (long long)st[0], (long long)sc[1], (long long)rcv[1]);
           }
       }
+  // the eigenvalue routine of the Chebyshev set-up: -1 2 -1 matrices of every size it takes (largest eigenvalue 2 - 2 cos(k pi / (k + 1))),
+  // and its refusals
+  for (int k = 1; k <= 256; ++k)
+    {
+      std::vector<double> d((size_t)k, 2.0), e((size_t)(k > 1 ? k - 1 : 0), -1.0);
+      double lo = 0, hi = 0;
+      if (pdh_tridiagonal_eigenvalues(k, d.data(), k > 1 ? e.data() : nullptr, &lo, &hi) != PDH_OK ||
+          std::fabs(hi - (2.0 - 2.0 * std::cos(k * M_PI / (k + 1)))) > 1e-12 || std::fabs(lo - (2.0 - 2.0 * std::cos(M_PI / (k + 1)))) > 1e-12)
+        {
+          std::printf("pdh_tridiagonal_eigenvalues: k %d lo %.17g hi %.17g\n", k, lo, hi);
+          return 1;
+        }
+    }
+  double lo, hi, one = 1.0;
+  if (pdh_tridiagonal_eigenvalues(0, &one, nullptr, &lo, &hi) != PDH_EINVAL || pdh_tridiagonal_eigenvalues(257, &one, &one, &lo, &hi) != PDH_EINVAL ||
+      pdh_tridiagonal_eigenvalues(2, &one, nullptr, &lo, &hi) != PDH_EINVAL)
+    return 1;
+  std::printf("tridiagonal eigenvalues: k = 1 .. 256 ok\n");
   return 0;
 }

@@ -5,7 +5,14 @@ FE_AggloDGP(3) of the same mesh; then a full headline solve.  bench.py is not in
 Times are HIP events on the library's stream (the context runs on torch's current stream), median of --reps launches after a warm-up.
 Rates are over the bytes the kernel must read: the values (vmult), the values + the inverse blocks (one CG iteration), and the fraction
 of the 8 TB/s HBM figure.  One CG iteration = (time of a solve with max_iter = k + m - time with max_iter = k) / m, host stop test
-included.  Prints one JSON document (and writes it to --out)."""
+included.
+
+Chebyshev section (--chebyshev; pdh_setup_chebyshev), in the same process and on the same resident matrices as the figures above, so
+that the two can be compared: k_cheb_update alone (a degree-1 application from a zero start is exactly one launch of it), one degree-5
+application (4 k_vmult + 5 updates, HIP events), the set-up with the inner build and the eigenvalue estimate apart, and full solves of
+b = A x* with block Jacobi and with Chebyshev of degree 2, 3 and 5: iterations, products with A and seconds.  The condition checked
+(field cheb5_within_bound): a degree-m application takes no longer than m x 1.10 block-Jacobi CG iterations measured here.
+Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
 import os
@@ -96,6 +103,54 @@ def run_case(pa, torch, ctx, cells, basis, diag_first, reps):
     return rec, ah
 
 
+def chebyshev_case(pa, torch, ctx, N, rec, reps, solves):
+    """the Chebyshev figures of the resident matrix; rec: the record of run_case (its CG iteration is the yardstick)"""
+    x = torch.rand(N, dtype=torch.float64, device="cuda")
+    z = torch.empty(N, dtype=torch.float64, device="cuda")
+    out = {"element": rec["element"], "layout": rec["layout"]}
+    inner = event_times_ms(torch, lambda: ctx.setup_preconditioner("block_jacobi"), max(3, reps // 3))
+    t = []
+    for _ in range(max(3, reps // 3) + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = ctx.setup_chebyshev("block_jacobi", degree=5)
+        t.append((time.perf_counter() - t0) * 1e3)
+    out.update(setup_inner_ms_median=median(inner), setup_total_ms_median=median(t[1:]), setup_estimate_ms=median(t[1:]) - median(inner),
+               estimate=info["estimate"], estimate_cg_steps=info["cg_iterations"])
+    est = info["estimate"]
+    for m in (1, 5):
+        ctx.setup_chebyshev("block_jacobi", degree=m, max_eigenvalue=est)
+        tm = event_times_ms(torch, lambda: ctx.precondition_device(x.data_ptr(), z.data_ptr()), reps)
+        out["cheb_update_ms_median" if m == 1 else "cheb5_application_ms_median"] = median(tm)
+        out["cheb_update_ms_min" if m == 1 else "cheb5_application_ms_min"] = min(tm)
+    out["cg_iteration_ms_median"] = rec["cg_iteration_ms_median"]
+    out["vmult_ms_median"] = rec["vmult_ms_median"]
+    out["cheb5_bound_ms"] = 5 * 1.10 * rec["cg_iteration_ms_median"]
+    out["cheb5_over_cg_iteration"] = out["cheb5_application_ms_median"] / rec["cg_iteration_ms_median"]
+    out["cheb5_within_bound"] = bool(out["cheb5_application_ms_median"] <= out["cheb5_bound_ms"])
+    if solves:
+        gen = torch.Generator(device="cuda").manual_seed(1)
+        xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=gen)
+        b = torch.empty(N, dtype=torch.float64, device="cuda")
+        ctx.vmult_device(xs.data_ptr(), b.data_ptr())
+        out["solves"] = []
+        for m in (0, 2, 3, 5):
+            if m:
+                ctx.setup_chebyshev("block_jacobi", degree=m, max_eigenvalue=est)
+            else:
+                ctx.setup_preconditioner("block_jacobi")
+            sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            si = ctx.solve_cg_device(b.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+            wall = time.perf_counter() - t0
+            its = si["iterations"]
+            out["solves"].append({"preconditioner": "Chebyshev(%d) over block Jacobi" % m if m else "block Jacobi", "iterations": its,
+                                  "products_with_A": 1 + its * max(m, 1), "wall_s": wall, "residual": si["residual"],
+                                  "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))})
+    return out
+
+
 def full_solve(pa, torch, ctx, N, reps_unused=None):
     """block-Jacobi CG on the resident headline matrix, b = A x* for a random x*, rel_tol 1e-13, x0 = 0"""
     gen = torch.Generator(device="cuda").manual_seed(1)
@@ -119,6 +174,7 @@ def main():
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-solve", action="store_true", help="skip the full headline solve")
+    ap.add_argument("--chebyshev", action="store_true", help="add the Chebyshev section (FE_DGQ(3) diag_first and FE_AggloDGP(3))")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -135,6 +191,10 @@ def main():
         if basis == "dgq" and diag_first and not args.no_solve:
             out["full_solve"] = full_solve(pa, torch, ctx, ah.n_dofs)
             print(json.dumps(out["full_solve"]), flush=True)
+        if args.chebyshev and diag_first:
+            ch = chebyshev_case(pa, torch, ctx, ah.n_dofs, rec, args.reps, not args.no_solve)
+            out.setdefault("chebyshev", []).append(ch)
+            print(json.dumps(ch), flush=True)
         del ah
     ctx.close()
     doc = json.dumps(out, indent=1)
