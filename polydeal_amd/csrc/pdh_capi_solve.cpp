@@ -1,0 +1,398 @@
+// pdh_capi_solve.cpp — device driver of the C ABI, solving with the resident matrix (kernels: pdh_solve.hip): y = A x, the Jacobi /
+// block Jacobi inverses, CG, and the Chebyshev smoother / preconditioner.  The one CG recurrence (CgRun) serves the solver and the
+// eigenvalue estimate of the Chebyshev set-up; the host arithmetic of the latter is the planner's (pdh_plan.h).
+#include "pdh_ctx.h"
+#include "pdh_launch.h"
+
+#include <cmath>
+
+static PdhSolveArgs solve_args(const pdh_ctx *ctx)
+{
+  PdhSolveArgs A;
+  A.values = ctx->prob.dev.values;
+  A.row_base = ctx->prob.dev.row_base;
+  A.row_len = ctx->prob.dev.row_len;
+  A.diag_L = ctx->prob.dev.diag_L;
+  A.own_row = ctx->prob.dev.own_row;
+  A.blk_ptr = ctx->prob.d_blk_ptr;
+  A.blk_dof = ctx->prob.d_blk_dof;
+  A.n = ctx->prob.dev.n;
+  A.diag_first = ctx->prob.dev.diag_first;
+  A.n_owned = ctx->prob.n_owned;
+  A.max_row_len = ctx->prob.max_row_len;
+  return A;
+}
+
+static bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
+{
+  const char *pa = static_cast<const char *>(a), *pb = static_cast<const char *>(b);
+  return pa < pb + nb * (int64_t)sizeof(double) && pb < pa + na * (int64_t)sizeof(double);
+}
+
+static constexpr int PDH_VMULT_LDS_CAP = 64 * 1024; // column set of one polytope in LDS (8192 columns)
+
+static int row_fits_lds(pdh_ctx *ctx)
+{
+  if ((int64_t)ctx->prob.max_row_len * (int64_t)sizeof(double) > PDH_VMULT_LDS_CAP)
+    return fail(ctx, PDH_EUNSUPPORTED, "a row has more than 8192 entries (the column set of a polytope must fit 64 KB of LDS)");
+  return PDH_OK;
+}
+
+// The solvers run on a context that owns all rows without the exchange variant.  The two families of messages differ in their
+// wording only: `runs_on` / `it` / `tail` are "the solver runs on" / "the solver" / " (no distributed Krylov solver)" for CG and
+// "it needs" / "it" / "" for the Chebyshev set-up.
+static int all_rows_checks(pdh_ctx *ctx, const char *who, const char *runs_on, const char *it, const char *tail)
+{
+  if (ctx->prob.ghost)
+    return fail(ctx, PDH_EUNSUPPORTED, std::string(who) + ": the problem was set in PDH_EXCHANGE_GHOST mode; " + runs_on +
+                                         " a context that owns all rows with PDH_EXCHANGE_NONE" + tail);
+  if (ctx->prob.n_rows_owned != ctx->prob.n_rows_total)
+    return fail(ctx, PDH_EUNSUPPORTED, std::string(who) + ": the context owns rows " + std::to_string(ctx->prob.n_rows_owned) + " of " +
+                                         std::to_string(ctx->prob.n_rows_total) + "; " + it + " needs all rows in one context" + tail);
+  return PDH_OK;
+}
+
+static int vmult_checks(pdh_ctx *ctx, const void *x, const void *y)
+{
+  PDH_TRY(need_problem(ctx, "pdh_vmult"));
+  if (!x || !y)
+    return fail(ctx, PDH_EINVAL, "x and y are required");
+  if (overlap(x, ctx->prob.n_rows_total, y, ctx->prob.n_rows_owned))
+    return fail(ctx, PDH_EINVAL, "x and y overlap");
+  return row_fits_lds(ctx);
+}
+
+extern "C" int pdh_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y)
+{
+  PDH_TRY(vmult_checks(ctx, d_x, d_y));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, d_y, nullptr, ctx->stream));
+  return PDH_OK;
+}
+
+extern "C" int pdh_vmult(pdh_ctx *ctx, const double *x, double *y)
+{
+  PDH_TRY(vmult_checks(ctx, x, y));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  double *d_x = nullptr, *d_y = nullptr;
+  PDH_TRY(stage_in(ctx, "pdh_vmult", ctx->io.in0, x, (size_t)ctx->prob.n_rows_total, &d_x));
+  PDH_TRY(stage(ctx, "pdh_vmult", ctx->io.in1, (size_t)ctx->prob.n_rows_owned, &d_y));
+  PDH_TRY(pdh_vmult_device(ctx, d_x, d_y));
+  PDH_HIP(ctx, hipMemcpyAsync(y, d_y, ctx->prob.n_rows_owned * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PDH_OK;
+}
+
+extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
+{
+  PDH_TRY(need_problem(ctx, "pdh_setup_preconditioner"));
+  if (kind != PDH_PREC_NONE && kind != PDH_PREC_JACOBI && kind != PDH_PREC_BLOCK_JACOBI)
+    return fail(ctx, PDH_EINVAL, "kind must be PDH_PREC_NONE, PDH_PREC_JACOBI or PDH_PREC_BLOCK_JACOBI");
+  if (kind == PDH_PREC_BLOCK_JACOBI && ctx->prob.dev.n > 64)
+    return fail(ctx, PDH_EUNSUPPORTED, "block Jacobi needs at most 64 dofs per polytope (use PDH_PREC_JACOBI)");
+  ctx->prec_kind = kind;
+  ctx->prec_gen = ctx->values_gen;
+  ctx->prec_ok = false; // until the set-up below has succeeded
+  if (kind == PDH_PREC_NONE)
+    {
+      ctx->prec_ok = true;
+      return PDH_OK;
+    }
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t n = ctx->prob.dev.n;
+  pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  double *dinv = S.dinv.get<double>(kind == PDH_PREC_BLOCK_JACOBI ? ctx->prob.n_owned * n * n : ctx->prob.n_rows_owned);
+  int32_t *flag = S.flag.get<int32_t>(ctx->prob.n_owned);
+  if (!dinv || !flag)
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_preconditioner: out of device memory");
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, kind == PDH_PREC_BLOCK_JACOBI ? pdh_launch_block_inverse(&A, dinv, flag, ctx->stream)
+                                             : pdh_launch_diag_inverse(&A, dinv, flag, ctx->stream));
+  std::vector<int32_t> h_flag((size_t)ctx->prob.n_owned);
+  if (ctx->prob.n_owned)
+    PDH_HIP(ctx, hipMemcpyAsync(h_flag.data(), flag, h_flag.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int s = 0; s < ctx->prob.n_owned; ++s)
+    if (h_flag[s])
+      { // slots are in polytope order: the first flagged slot is the lowest polytope number
+        int32_t agg = -1;
+        PDH_HIP(ctx, hipMemcpy(&agg, ctx->prob.dev.own_agg + s, sizeof(int32_t), hipMemcpyDeviceToHost));
+        return fail(ctx, PDH_EINVAL,
+                    kind == PDH_PREC_BLOCK_JACOBI
+                      ? "block Jacobi: the diagonal block of polytope " + std::to_string(agg) + " is not positive definite"
+                      : "Jacobi: a diagonal entry of polytope " + std::to_string(agg) + " is zero or not finite");
+      }
+  ctx->prec_ok = true;
+  return PDH_OK;
+}
+
+static int prec_checks(pdh_ctx *ctx)
+{
+  if (ctx->prec_kind != PDH_PREC_NONE && (!ctx->prec_ok || ctx->prec_gen != ctx->values_gen))
+    return fail(ctx, PDH_ESTATE, ctx->prec_ok ? "the values changed since pdh_setup_preconditioner: set it up again"
+                                              : "the last pdh_setup_preconditioner failed");
+  return PDH_OK;
+}
+
+// One application of the Chebyshev polynomial to b, queued on the stream: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b,
+// x not read).  d, r and q are the context's own vectors - never CG's residual.  rcg / part: see pdh_launch_cheb_update.
+static int cheb_apply(pdh_ctx *ctx, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part)
+{
+  const pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  double *d = S.cheb_d.ptr<double>(), *r = S.cheb_r.ptr<double>(), *q = S.q.ptr<double>();
+  const double *dinv = S.dinv.ptr<double>();
+  const int m = (int)S.cheb_c2.size();
+  if (!d || !r || !q || !dinv || m < 1)
+    return fail(ctx, PDH_ESTATE, "the Chebyshev preconditioner is not set up");
+  if (!zero)
+    PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, ctx->stream));
+  for (int k = 0; k < m; ++k)
+    {
+      if (k > 0)
+        PDH_HIP(ctx, pdh_launch_vmult(&A, d, q, nullptr, ctx->stream));
+      PDH_HIP(ctx, pdh_launch_cheb_update(&A, k == 0, S.cheb_inner, dinv, b, (k == 0 && zero) ? nullptr : q, d, r, x, S.cheb_c1[k], S.cheb_c2[k],
+                                          k == 0 && zero, k == m - 1 ? rcg : nullptr, part, ctx->stream));
+    }
+  return PDH_OK;
+}
+
+extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *d_z)
+{
+  PDH_TRY(need_problem(ctx, "pdh_precondition_device"));
+  if (!d_r || !d_z)
+    return fail(ctx, PDH_EINVAL, "r and z are required");
+  PDH_TRY(prec_checks(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const PdhSolveArgs A = solve_args(ctx);
+  if (ctx->prec_kind == PDH_PREC_CHEBYSHEV)
+    return cheb_apply(ctx, A, d_r, d_z, true, nullptr, nullptr);
+  PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_APPLY, ctx->prec_kind, ctx->prob.sol.dinv.ptr<double>(), nullptr, nullptr,
+                                    nullptr, nullptr, const_cast<double *>(d_r), d_z, nullptr, nullptr, ctx->stream));
+  return PDH_OK;
+}
+
+// The preconditioned CG recurrence on the resident matrix, queued on the context's stream: the loop of examples/host_solver.h (q = A p,
+// alpha, x and r, z, beta, p) with every scalar kept on the device.  After each of start() / step() `n_scalars` doubles from
+// scal[first_scalar] are in ctx->pinned and the stream is idle - what they are and what follows from them is the caller's.
+// kind: the preconditioner of the fused update; chain: the Chebyshev chain z = p(P^-1 A) P^-1 r follows it instead (kind none leaves z
+// alone), its last step writes the partials of r^T z.
+struct CgRun
+{
+  pdh_ctx *ctx;
+  const PdhSolveArgs A;
+  const int kind;
+  const bool chain;
+  const int64_t N;
+  const int n_owned;
+  hipStream_t st;
+  double *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *part = nullptr, *scal = nullptr;
+  const double *dinv = nullptr;
+
+  CgRun(pdh_ctx *c, int kind_, bool chain_)
+    : ctx(c), A(solve_args(c)), kind(kind_), chain(chain_), N(c->prob.n_rows_owned), n_owned(c->prob.n_owned), st(c->stream)
+  {
+    pdh_ctx::Problem::Solver &S = c->prob.sol;
+    r = S.r.get<double>(N), z = S.z.get<double>(N), p = S.p.get<double>(N), q = S.q.get<double>(N);
+    part = S.part.get<double>((size_t)PDH_CG_NPART * n_owned);
+    scal = S.scal.get<double>(PDH_CG_NSCALARS);
+    if (!c->pinned && hipHostMalloc((void **)&c->pinned, PDH_CG_NSCALARS * sizeof(double), hipHostMallocDefault) != hipSuccess)
+      c->pinned = nullptr;
+    dinv = S.dinv.ptr<double>();
+  }
+  bool ok() const { return r && z && p && q && part && scal && ctx->pinned; }
+  int read_back(int first_scalar, int n_scalars)
+  {
+    PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + first_scalar, n_scalars * sizeof(double), hipMemcpyDeviceToHost, st));
+    PDH_HIP(ctx, hipStreamSynchronize(st));
+    return PDH_OK;
+  }
+  // r = b - A x, z = P^-1 r, p = z
+  int start(const double *b, const double *x, int first_scalar, int n_scalars)
+  {
+    PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, st));
+    PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, b, q, nullptr, nullptr, r, z, scal, part, st));
+    if (chain)
+      PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
+    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 0, scal, st));
+    PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
+    return read_back(first_scalar, n_scalars);
+  }
+  int step(double *x, int first_scalar, int n_scalars)
+  {
+    PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * n_owned, st));
+    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 1, scal, st));
+    PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, x, r, z, scal, part, st));
+    if (chain)
+      PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
+    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 2, scal, st));
+    PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
+    return read_back(first_scalar, n_scalars);
+  }
+};
+
+extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const double *d_b, double *d_x, pdh_cg_result *res)
+{
+  PDH_TRY(need_problem(ctx, "pdh_solve_cg"));
+  if (!c || !d_b || !d_x || !res)
+    return fail(ctx, PDH_EINVAL, "control, b, x and result are required");
+  if (c->max_iter < 0 || !(c->rel_tol >= 0.0) || !(c->abs_tol >= 0.0))
+    return fail(ctx, PDH_EINVAL, "max_iter, rel_tol and abs_tol must be non-negative");
+  PDH_TRY(all_rows_checks(ctx, "pdh_solve_cg", "the solver runs on", "the solver", " (no distributed Krylov solver)"));
+  if (overlap(d_b, ctx->prob.n_rows_total, d_x, ctx->prob.n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(row_fits_lds(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const bool cheb = ctx->prec_kind == PDH_PREC_CHEBYSHEV;
+  CgRun cg(ctx, cheb ? PDH_PREC_NONE : ctx->prec_kind, cheb);
+  if (!cg.ok())
+    return fail(ctx, PDH_EDEVICE, "pdh_solve_cg: out of device memory");
+  PDH_TRY(cg.start(d_b, d_x, PDH_CG_RR, 2));
+  double rr = ctx->pinned[0];
+  const double bnorm = std::sqrt(ctx->pinned[1]);
+  const double stop = std::max(c->abs_tol, c->rel_tol * bnorm);
+  res->residual0 = std::sqrt(rr);
+  int it = 0;
+  // test, then one step.  Only ||r||^2 crosses PCIe (8 bytes, pinned).
+  for (; it < c->max_iter && std::sqrt(rr) > stop; ++it)
+    {
+      PDH_TRY(cg.step(d_x, PDH_CG_RR, 1));
+      rr = ctx->pinned[0];
+    }
+  res->iterations = it;
+  res->residual = std::sqrt(rr);
+  if (!(res->residual <= stop))
+    return fail(ctx, PDH_ENOCONV, "pdh_solve_cg: no convergence in " + std::to_string(it) + " iterations (||r|| = " +
+                                    std::to_string(res->residual) + ", bound " + std::to_string(stop) + ")");
+  return PDH_OK;
+}
+
+extern "C" int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *c, const double *b, double *x, pdh_cg_result *res)
+{
+  PDH_TRY(need_problem(ctx, "pdh_solve_cg"));
+  if (!b || !x)
+    return fail(ctx, PDH_EINVAL, "b and x are required");
+  if (overlap(b, ctx->prob.n_rows_total, x, ctx->prob.n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t N = ctx->prob.n_rows_total;
+  double *d_b = nullptr, *d_x = nullptr;
+  PDH_TRY(stage_in(ctx, "pdh_solve_cg", ctx->io.in0, b, (size_t)N, &d_b));
+  PDH_TRY(stage_in(ctx, "pdh_solve_cg", ctx->io.in1, x, (size_t)N, &d_x));
+  const int rc = pdh_solve_cg_device(ctx, c, d_b, d_x, res);
+  if (rc != PDH_OK && rc != PDH_ENOCONV)
+    return rc;
+  const std::string msg = ctx->err;
+  PDH_HIP(ctx, hipMemcpyAsync(x, d_x, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (rc == PDH_ENOCONV)
+    ctx->err = msg;
+  return rc;
+}
+
+// ---- Chebyshev smoother / preconditioner (include/polydeal_hip.h: pdh_setup_chebyshev) ----------------------------------------------
+// Largest Ritz value of P^-1 A after k steps of P-preconditioned CG on A x = b0 from x = 0 (P = the inner preconditioner, set up and
+// current): the solver's recurrence, but alpha_j, beta_j and ||r||^2 come back every step.  steps: CG steps that entered the
+// Lanczos matrix.
+static int cheb_estimate(pdh_ctx *ctx, int kind, int k, double *est, int *steps)
+{
+  const int64_t N = ctx->prob.n_rows_owned;
+  CgRun cg(ctx, kind, false);
+  double *d_b = ctx->io.in0.get<double>((size_t)N), *d_x = ctx->io.in1.get<double>((size_t)N);
+  if (!cg.ok() || !d_b || !d_x)
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_chebyshev: out of device memory");
+  std::vector<double> b0((size_t)N);
+  for (int64_t i = 0; i < N; ++i)
+    b0[(size_t)i] = (double)(uint32_t)(2654435761ull * (uint64_t)i) / 4294967296.0 - 0.5;
+  PDH_HIP(ctx, hipMemcpyAsync(d_b, b0.data(), N * sizeof(double), hipMemcpyHostToDevice, cg.st));
+  PDH_HIP(ctx, hipMemsetAsync(d_x, 0, N * sizeof(double), cg.st));
+  PDH_TRY(cg.start(d_b, d_x, 0, PDH_CG_NSCALARS));
+  double rr = ctx->pinned[PDH_CG_RR];
+  std::vector<double> alpha, beta;
+  for (int it = 0; it < k && rr > 0.0; ++it)
+    {
+      PDH_TRY(cg.step(d_x, 0, PDH_CG_NSCALARS));
+      const double a = ctx->pinned[PDH_CG_ALPHA], b = ctx->pinned[PDH_CG_BETA];
+      if (!(a > 0.0) || !std::isfinite(a) || !(b >= 0.0) || !std::isfinite(b))
+        break; // p^T A p <= 0 or a breakdown: the steps so far
+      alpha.push_back(a);
+      beta.push_back(b);
+      rr = ctx->pinned[PDH_CG_RR];
+    }
+  const int m = (int)alpha.size();
+  if (m < 1)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: the eigenvalue estimate took no CG step (no rows, or the matrix is not positive "
+                                 "definite on the test vector)");
+  std::vector<double> dg, od;
+  pdh_lanczos_tridiagonal(alpha, beta, dg, od);
+  double lo = 0.0, hi = 0.0;
+  if (pdh_tridiagonal_eigenvalues(m, dg.data(), od.data(), &lo, &hi) != PDH_OK)
+    return fail(ctx, PDH_EINVAL, std::string("pdh_setup_chebyshev: ") + pdh_last_error(nullptr));
+  *est = hi;
+  *steps = m;
+  return PDH_OK;
+}
+
+extern "C" int pdh_setup_chebyshev(pdh_ctx *ctx, const pdh_chebyshev_control *c, pdh_chebyshev_info *info)
+{
+  PDH_TRY(need_problem(ctx, "pdh_setup_chebyshev"));
+  if (!c)
+    return fail(ctx, PDH_EINVAL, "control is required");
+  if (c->inner != PDH_PREC_JACOBI && c->inner != PDH_PREC_BLOCK_JACOBI)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: inner must be PDH_PREC_JACOBI or PDH_PREC_BLOCK_JACOBI");
+  if (c->degree < 1)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: degree must be at least 1");
+  if (!(c->smoothing_range > 1.0) || !std::isfinite(c->smoothing_range))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: smoothing_range must be finite and greater than 1");
+  if (std::isnan(c->max_eigenvalue) || std::isinf(c->max_eigenvalue))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: max_eigenvalue is not finite");
+  const bool given = c->max_eigenvalue > 0.0;
+  if (!given && (c->eig_cg_n_iterations < 1 || c->eig_cg_n_iterations > 256))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: eig_cg_n_iterations must be 1 .. 256 (or give max_eigenvalue > 0)");
+  PDH_TRY(all_rows_checks(ctx, "pdh_setup_chebyshev", "it needs", "it", ""));
+  PDH_TRY(row_fits_lds(ctx));
+  PDH_TRY(pdh_setup_preconditioner(ctx, c->inner)); // the inner inverse; prec_kind = inner for the estimate
+  ctx->prec_ok = false;                             // until the whole set-up has succeeded
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  double est = c->max_eigenvalue;
+  int steps = 0;
+  if (!given)
+    PDH_TRY(cheb_estimate(ctx, c->inner, c->eig_cg_n_iterations, &est, &steps));
+  if (!(est > 0.0) || !std::isfinite(est))
+    return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: the eigenvalue estimate " + std::to_string(est) + " is not positive");
+  const int64_t N = ctx->prob.n_rows_owned;
+  pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (!S.cheb_d.get<double>(N) || !S.cheb_r.get<double>(N) || !S.q.get<double>(N))
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_chebyshev: out of device memory");
+  double lo = 0.0, hi = 0.0;
+  pdh_chebyshev_coefficients(c->degree, est, c->smoothing_range, &lo, &hi, S.cheb_c1, S.cheb_c2);
+  S.cheb_inner = c->inner;
+  ctx->prec_kind = PDH_PREC_CHEBYSHEV;
+  ctx->prec_gen = ctx->values_gen;
+  ctx->prec_ok = true;
+  if (info)
+    {
+      info->estimate = est;
+      info->lambda_lo = lo;
+      info->lambda_hi = hi;
+      info->cg_iterations = steps;
+      info->degree = c->degree;
+      info->inner = c->inner;
+    }
+  return PDH_OK;
+}
+
+extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double *d_x, int zero_initial_guess)
+{
+  PDH_TRY(need_problem(ctx, "pdh_chebyshev_step_device"));
+  if (!d_b || !d_x)
+    return fail(ctx, PDH_EINVAL, "b and x are required");
+  if (overlap(d_b, ctx->prob.n_rows_total, d_x, ctx->prob.n_rows_total))
+    return fail(ctx, PDH_EINVAL, "b and x overlap");
+  if (ctx->prec_kind != PDH_PREC_CHEBYSHEV)
+    return fail(ctx, PDH_ESTATE, "pdh_chebyshev_step_device: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
+  PDH_TRY(prec_checks(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  return cheb_apply(ctx, solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
+}

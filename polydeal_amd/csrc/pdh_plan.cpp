@@ -1829,3 +1829,37 @@ extern "C" int pdh_tridiagonal_eigenvalues(int k, const double *diag, const doub
   *hi = kth(k - 1);
   return PDH_OK;
 }
+
+void pdh_lanczos_tridiagonal(const std::vector<double> &alpha, const std::vector<double> &beta, std::vector<double> &diag,
+                             std::vector<double> &offdiag)
+{
+  const int m = (int)alpha.size();
+  diag.assign((size_t)m, 0.0);
+  offdiag.assign((size_t)std::max(m - 1, 1), 0.0);
+  for (int j = 0; j < m; ++j)
+    {
+      diag[j] = j == 0 ? 1.0 / alpha[j] : 1.0 / alpha[j] + beta[j - 1] / alpha[j - 1];
+      if (j + 1 < m)
+        offdiag[j] = std::sqrt(beta[j]) / alpha[j];
+    }
+}
+
+void pdh_chebyshev_coefficients(int degree, double estimate, double smoothing_range, double *lambda_lo, double *lambda_hi,
+                                std::vector<double> &c1, std::vector<double> &c2)
+{
+  const double hi = 1.2 * estimate, lo = hi / smoothing_range;
+  const double theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta;
+  c1.assign((size_t)degree, 0.0);
+  c2.assign((size_t)degree, 0.0);
+  c2[0] = 1 / theta;
+  double rho_old = 1 / sigma;
+  for (int k = 1; k < degree; ++k)
+    {
+      const double rho = 1 / (2 * sigma - rho_old);
+      c1[k] = rho * rho_old;
+      c2[k] = 2 * rho / delta;
+      rho_old = rho;
+    }
+  *lambda_lo = lo;
+  *lambda_hi = hi;
+}

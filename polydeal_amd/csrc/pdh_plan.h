@@ -190,3 +190,13 @@ int combo_group(int dim, int n1d, int nt, int lb);
 
 // the error string of calls without a context (per thread): what pdh_last_error(NULL) returns
 std::string &pdh_noctx_error();
+
+// ---- host arithmetic of pdh_setup_chebyshev (the driver calls these; plain C++, not part of the C ABI) --------------------------------
+// Lanczos matrix of m >= 1 steps of preconditioned CG (step lengths alpha, ratios beta = r'z_new / r'z_old): its diagonal [m] and
+// off-diagonal [max(m - 1, 1)], the input of pdh_tridiagonal_eigenvalues
+void pdh_lanczos_tridiagonal(const std::vector<double> &alpha, const std::vector<double> &beta, std::vector<double> &diag,
+                             std::vector<double> &offdiag);
+// Chebyshev iteration of `degree` steps on [lambda_hi / smoothing_range, lambda_hi], lambda_hi = 1.2 estimate: per step k the
+// factors c1[k] of d_(k-1) and c2[k] of P^-1 r_k in d_k (step 0: 0 and 1 / theta, theta the centre of the interval)
+void pdh_chebyshev_coefficients(int degree, double estimate, double smoothing_range, double *lambda_lo, double *lambda_hi,
+                                std::vector<double> &c1, std::vector<double> &c2);

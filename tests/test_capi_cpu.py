@@ -197,3 +197,56 @@ def test_every_entry_point_has_declared_argument_types():
     lib = pa.load_library()
     missing = [s for s in _capi.EXPORTS if s != "pdh_version" and getattr(lib, s).argtypes is None]
     assert not missing, missing
+
+
+_NULL = (_capi.PDH_EINVAL, "ctx is NULL")
+_NONE_RESIDENT = (_capi.PDH_ESTATE, "no problem resident")
+_NO_GHOST = (_capi.PDH_ESTATE, "no problem resident in PDH_EXCHANGE_GHOST mode")
+# what every entry point that takes a context answers for ctx = NULL, every other pointer valid (transcribed from the driver's source
+# before it was split into units: some answer like "no problem resident", two name their other required argument)
+NULL_CTX_ANSWERS = {
+    "pdh_set_problem": _NULL, "pdh_set_problem_local": _NULL, "pdh_set_problem_cartesian": _NULL,
+    "pdh_assemble_device": _NULL, "pdh_assemble": _NULL, "pdh_assemble_sip": _NULL, "pdh_assemble_sip_local": _NULL,
+    "pdh_device_values": _NONE_RESIDENT, "pdh_synchronize": _NULL, "pdh_set_profiling": _NULL,
+    "pdh_kernel_times_ms": (_capi.PDH_EINVAL, "ctx or ms is NULL"), "pdh_problem_stats": _NONE_RESIDENT,
+    "pdh_assemble_rhs": _NULL, "pdh_kernel_work": _NONE_RESIDENT, "pdh_evaluate": _NULL, "pdh_shape_values": _NULL,
+    "pdh_set_algorithm": _NULL, "pdh_algorithm_in_use": _NONE_RESIDENT, "pdh_set_overlap": _NULL, "pdh_set_exchange_mode": _NULL,
+    "pdh_exchange_layout": _NONE_RESIDENT, "pdh_exchange_get_send": _NO_GHOST, "pdh_exchange_apply": _NO_GHOST,
+    "pdh_set_stream": _NULL, "pdh_copy_values": _NONE_RESIDENT, "pdh_values_checksum": _NONE_RESIDENT,
+    "pdh_assemble_rhs_device": _NULL, "pdh_evaluate_device": _NULL, "pdh_shape_values_device": _NULL, "pdh_global_error": _NULL,
+    "pdh_global_error_device": _NULL, "pdh_rows_kernel_in_use": _NONE_RESIDENT,
+    "pdh_terms_merge_stats": (_capi.PDH_EINVAL, "ctx and out4 are required"),
+    "pdh_vmult": _NULL, "pdh_vmult_device": _NULL, "pdh_setup_preconditioner": _NULL, "pdh_precondition_device": _NULL,
+    "pdh_solve_cg": _NULL, "pdh_solve_cg_device": _NULL, "pdh_setup_chebyshev": _NULL, "pdh_chebyshev_step_device": _NULL,
+    "pdh_debug_rows_stamps": (_capi.PDH_ESTATE, "no row-kernel problem resident"),  # (diagnostic, not in the public header)
+}
+
+
+def test_every_entry_point_answers_a_null_context_as_before():
+    """ctx = NULL is an argument error answered on the host, with the code and the text of pdh_last_error(NULL) each entry point has
+    always given.  Every other argument is valid, so that the answer is the one about the context."""
+    lib = pa.load_library()
+    lib.pdh_debug_rows_stamps.argtypes = [C.c_void_p, C.c_void_p]
+    takes_ctx = {s for s in _capi.EXPORTS if (getattr(lib, s).argtypes or [None])[0] is C.c_void_p and not s.startswith("pdh_check_")}
+    takes_ctx -= {"pdh_destroy", "pdh_last_error", "pdh_stream"}  # no code to return: below
+    assert takes_ctx | {"pdh_debug_rows_stamps"} == set(NULL_CTX_ANSWERS)
+    kw = small_problem()
+    problem = pa.Problem(**kw)
+    room = (C.c_double * 64)()  # what any output or input pointer may point to: never reached
+    for name, (code, text) in sorted(NULL_CTX_ANSWERS.items()):
+        fn = getattr(lib, name)
+        args = [None]
+        for t in fn.argtypes[1:]:
+            if t is C.c_void_p:
+                args.append(C.addressof(room))
+            elif t is C.POINTER(_capi.pdh_problem):
+                args.append(C.byref(problem.c))
+            elif hasattr(t, "contents"):  # POINTER(struct or scalar)
+                args.append(C.cast(room, t))
+            else:
+                args.append(0)
+        lib.pdh_last_error(None)
+        rc = fn(*args)
+        assert (rc, lib.pdh_last_error(None).decode()) == (code, text), name
+    lib.pdh_destroy(None)
+    assert lib.pdh_stream(None) is None

@@ -1,5 +1,6 @@
 // ASan / UBSan smoke of the planner of the C ABI (pdh_plan.cpp: validation, packing, choice of the row kernel) on flattened problems.
 #include "../../polydeal_amd/csrc/host/polydeal_host.h"
+#include "../../polydeal_amd/csrc/pdh_plan.h"
 #include <cmath>
 #include <cstdio>
 using namespace polydeal_hip;
@@ -75,5 +76,68 @@ int main()
       pdh_tridiagonal_eigenvalues(2, &one, nullptr, &lo, &hi) != PDH_EINVAL)
     return 1;
   std::printf("tridiagonal eigenvalues: k = 1 .. 256 ok\n");
+  // the host arithmetic of the Chebyshev set-up.  Coefficients: every degree and range is finite, lo < hi, the first step is 1 / theta
+  for (int degree = 1; degree <= 8; ++degree)
+    for (double range : {2.0, 20.0, 1e6})
+      {
+        std::vector<double> c1, c2;
+        double clo = 0, chi = 0;
+        pdh_chebyshev_coefficients(degree, 1.75, range, &clo, &chi, c1, c2);
+        bool ok = (int)c1.size() == degree && (int)c2.size() == degree && std::isfinite(clo) && std::isfinite(chi) && clo < chi &&
+                  c2[0] == 1 / ((chi + clo) / 2);
+        for (int k = 0; k < degree && ok; ++k)
+          ok = std::isfinite(c1[k]) && std::isfinite(c2[k]);
+        if (!ok)
+          {
+            std::printf("pdh_chebyshev_coefficients: degree %d range %g\n", degree, range);
+            return 1;
+          }
+      }
+  // Lanczos matrix: alpha and beta of m = 1 .. 64 CG steps on the -1 2.5 -1 matrix of size 64 (SPD, eigenvalues in (0.5, 4.5))
+  {
+    const int n = 64;
+    auto mult = [&](const std::vector<double> &v, std::vector<double> &Av) {
+      for (int i = 0; i < n; ++i)
+        Av[i] = 2.5 * v[i] - (i > 0 ? v[i - 1] : 0.0) - (i + 1 < n ? v[i + 1] : 0.0);
+    };
+    auto dot = [&](const std::vector<double> &a, const std::vector<double> &b) {
+      double s = 0;
+      for (int i = 0; i < n; ++i)
+        s += a[i] * b[i];
+      return s;
+    };
+    std::vector<double> r((size_t)n), p, q((size_t)n), alpha, beta;
+    for (int i = 0; i < n; ++i)
+      r[i] = (double)((i * 37) % 11) - 4.5;
+    p = r;
+    double rr = dot(r, r);
+    for (int m = 1; m <= 64; ++m)
+      {
+        mult(p, q);
+        const double a = rr / dot(p, q);
+        for (int i = 0; i < n; ++i)
+          r[i] -= a * q[i];
+        const double rr_new = dot(r, r), b = rr_new / rr;
+        for (int i = 0; i < n; ++i)
+          p[i] = r[i] + b * p[i];
+        rr = rr_new;
+        alpha.push_back(a);
+        beta.push_back(b);
+        std::vector<double> dg, od;
+        pdh_lanczos_tridiagonal(alpha, beta, dg, od);
+        bool ok = (int)dg.size() == m && (int)od.size() == (m > 1 ? m - 1 : 1);
+        for (double v : dg)
+          ok = ok && std::isfinite(v);
+        for (double v : od)
+          ok = ok && std::isfinite(v);
+        double tlo = 0, thi = 0;
+        if (!ok || pdh_tridiagonal_eigenvalues(m, dg.data(), od.data(), &tlo, &thi) != PDH_OK || !(thi > 0.0))
+          {
+            std::printf("pdh_lanczos_tridiagonal: m %d hi %.17g\n", m, thi);
+            return 1;
+          }
+      }
+  }
+  std::printf("chebyshev coefficients: degrees 1 .. 8 ok; lanczos matrices: m = 1 .. 64 ok\n");
   return 0;
 }
