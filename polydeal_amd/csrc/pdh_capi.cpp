@@ -502,7 +502,7 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   Packed &K = *K_owner;
   PDH_TRY(pack_problem(ctx->err, p, row_begin, row_end, K, ctx->exchange_mode, cart));
   lap("validate + repack (host)");
-  auto plan = std::make_unique<KernelPlan>(plan_kernels(p, K, true));
+  auto plan = std::make_unique<KernelPlan>(plan_kernels(p, K, read_plan_switches()));
   lap("row kernel plan (host)");
   if (cart && plan->kernel != RowKernel::terms)
     return fail(ctx, PDH_EUNSUPPORTED, "cartesian description: the term kernels do not apply (a polytope's tables exceed their LDS budget, "

@@ -45,12 +45,7 @@ void host_parallel_for(size_t n, F &&fn)
 
 // which row kernel serves a problem (plan_kernels): none, the kinds of pdh_rows.h, or the term kernels (pdh_terms.h /
 // pdh_terms_wg.h)
-enum class RowKernel
-{
-  none,
-  rows,
-  terms
-};
+enum class RowKernel { none, rows, terms };
 
 // std::vector whose resize() leaves the new elements uninitialised: the big point arrays are filled by all host threads
 // right after they are sized, a serial zero-fill of 1.3 GB in between costs more than the fill itself
@@ -58,10 +53,7 @@ template <class T>
 struct UninitAlloc : std::allocator<T>
 {
   template <class U>
-  struct rebind
-  {
-    using other = UninitAlloc<U>;
-  };
+  struct rebind { using other = UninitAlloc<U>; };
   template <class U, class... A>
   void construct(U *ptr, A &&...a)
   {
@@ -102,7 +94,7 @@ struct Packed
   std::vector<int32_t> run_cnt, run_bdry;
   // per run (owned slots only, same order): owning slot, neighbour polytope (-1 boundary) and the ascending rank of the
   // neighbour's block in the slot's rows, penalty as stored per point - input of the row kernel's face table (pdh_rows.h)
-  std::vector<int32_t> run_slot, run_nbr, run_blk, run_face;
+  std::vector<int32_t> run_slot, run_nbr, run_blk;
   std::vector<double> run_sig;
   // pdh_set_problem_cartesian: the point arrays of `src` are NULL, the points are generated on the device from these
   const pdh_cartesian_points *cart = nullptr;
@@ -129,7 +121,7 @@ struct Packed
   // ghost-block exchange (PDH_EXCHANGE_GHOST): doubles per peer rank, and where the received blocks go
   std::vector<int64_t> send_count, recv_count;
   int64_t n_send = 0, n_recv = 0;
-  std::vector<int32_t> r21_face, r21_rlen, r22_slot;
+  std::vector<int32_t> r21_rlen, r22_slot;
   std::vector<int64_t> r21_src, r21_dst, r22_ptr, r22_src;
 };
 
@@ -182,8 +174,17 @@ struct KernelPlan
 int pack_problem(std::string &err, const pdh_problem *p, int32_t row_begin, int32_t row_end, Packed &K,
                  int exchange_mode = PDH_EXCHANGE_NONE, const pdh_cartesian_points *cart = nullptr);
 
-// switches: apply the diagnostic switches of pdh_set_problem (PDH_TERMS, PDH_TERMS_DGQ3), read on every call
-KernelPlan plan_kernels(const pdh_problem *p, const Packed &K, bool switches);
+// The diagnostic switches of the planner: PDH_TERMS_MERGE (0, 2, else 1), PDH_TERMS_SPLIT (0 / 1, unset: -1), PDH_TRACE_SETUP,
+// PDH_ROWS_VERBOSE, PDH_TERMS=0, PDH_TERMS_DGQ3=0.  read_plan_switches is the planner's only reader of the environment;
+// pdh_set_problem* and pdh_check_* call it on every call (the tests compare the kernels in one process).
+struct PlanSwitches
+{
+  int terms_merge = 1, terms_split = -1;
+  bool trace = false, rows_verbose = false, terms_off = false, terms_dgq3_off = false;
+};
+PlanSwitches read_plan_switches();
+
+KernelPlan plan_kernels(const pdh_problem *p, const Packed &K, const PlanSwitches &sw);
 
 // translation-unit group holding the kernels of a combo (pdh_combos.h), or -1 if that combo is not instantiated
 int combo_group(int dim, int n1d, int nt, int lb);
