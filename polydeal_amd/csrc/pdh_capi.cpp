@@ -13,7 +13,6 @@
 #include "pdh_combos.h"
 #include "pdh_ctx.h"
 #include "pdh_kernels.h" // pdh::Sched, for the MFMA work counts (the only driver unit that sees a kernel header)
-#include "pdh_launch.h"
 #include "pdh_moment_tables.h"
 
 #include <hip/hip_runtime.h>
@@ -28,8 +27,8 @@
 #include <string>
 #include <vector>
 
-static pdh_launch_fn g_launch[PDH_N_GROUPS] = {pdh_launch_g0, pdh_launch_g1, pdh_launch_g2, pdh_launch_g3,
-                                               pdh_launch_g4, pdh_launch_g5, pdh_launch_g6, pdh_launch_g7};
+static pdh_resolve_fn g_resolve[PDH_N_GROUPS] = {pdh_resolve_g0, pdh_resolve_g1, pdh_resolve_g2, pdh_resolve_g3,
+                                                 pdh_resolve_g4, pdh_resolve_g5, pdh_resolve_g6, pdh_resolve_g7};
 
 // number of MFMA instructions one 4-point step of a product issues, from the kernels' own schedule
 template <int NT, int LB>
@@ -322,11 +321,7 @@ static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
   ctx->prob.n_vq = K.n_vq;
   ctx->prob.n_ap = K.n_ap;
   ctx->prob.NT = K.NT;
-  ctx->prob.LB = K.LB;
   ctx->prob.tiled = K.tiled;
-  ctx->prob.group = K.tiled ? -1 : combo_group(p->dim, K.n1d, K.NT, K.LB);
-  ctx->prob.lds_diag = pdh::lds_bytes_diag(p->dim, K.n1d, K.NT);
-  ctx->prob.lds_off = pdh::lds_bytes_offdiag(p->dim, K.n1d, K.NT);
   ctx->prob.basis = p->basis;
   ctx->prob.n_vq_caller = p->vq_ptr[p->n_agg];
   ctx->prob.n_fq_caller = p->n_faces ? p->fq_ptr[p->n_faces] : 0;
@@ -373,8 +368,8 @@ static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
 }
 
 // pdh_rows.h: face tables and per-slot records, the work counter of the persistent waves, the stamps of -DPDHR_STAMP builds and,
-// for the MULTI instantiation, a scratch row per resident wave
-static int upload_rows_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &plan)
+// for the MULTI instantiation, a scratch row per resident wave (cus: compute units of the device)
+static int upload_rows_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &plan, int cus)
 {
   const RowsHost &RH = plan.rows;
   PdhRows &R = ctx->prob.rows;
@@ -399,8 +394,6 @@ static int upload_rows_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &pl
       // MULTI instantiation: the coupling moments of a polytope's interior entries (8 x 8 doubles each, up to 40 of
       // them) are parked between P2 and P5 in a per-wave row of this buffer instead of LDS (pdh_rows.h) - 8 waves per
       // CU at most (256 VGPRs), a few tens of MB that stay in L2 / the memory-side cache
-      int cus = 256;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
       const int waves = cus * 8;
       // (with tensor sub-face rules the row holds 16 + 16 factors per interior sub-face instead, pdh_rows.h: FACT)
       const size_t stride = std::max<size_t>((size_t)RH.maxf * 64, (size_t)RH.maxs * 32 + 64);
@@ -451,6 +444,25 @@ static int upload_terms_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &p
   return PDH_OK;
 }
 
+// Every launch pdh_set_algorithm can ask of the resident problem (pdh_ctx::Problem::direct / moment / row), resolved by the units that
+// instantiate the kernels
+static void resolve_launches(pdh_ctx *ctx, const Packed &K, const PlanSwitches &sw, int cus)
+{
+  pdh_ctx::Problem &pr = ctx->prob;
+  const PdhDev &D = pr.dev;
+  const bool reaction = D.reaction_c != 0.0;
+  if (K.tiled)
+    pdh_resolve_tiled(D.dim, D.n1d, D.n, reaction, pr.n_diag_slots, pr.n_items, pr.direct);
+  else // (pack_problem refused what no group instantiates)
+    g_resolve[combo_group(D.dim, D.n1d, K.NT, K.LB)](D.dim, D.n1d, K.NT, K.LB, reaction, pr.n_diag_slots, pr.n_items, pr.direct);
+  if (pr.d_mtab)
+    pdh_resolve_moment(D.n1d, D.n, pr.n_diag_slots, pr.n_items, pr.moment);
+  if (pr.row_kernel == RowKernel::rows)
+    pr.row = pdh_resolve_rows(&D, &pr.rows, pr.n_owned, cus, sw.rows_waves_per_cu, sw.rows_lds_pad, sw.rows_verbose, &pr.row_zero_sched);
+  else if (pr.row_kernel == RowKernel::terms)
+    pr.row = pdh_resolve_terms(&D, &pr.terms, pr.n_owned, sw.terms_wg_waves);
+}
+
 static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begin, int32_t row_end, const pdh_cartesian_points *cart);
 
 extern "C" int pdh_set_problem_local(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begin, int32_t row_end)
@@ -485,11 +497,11 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
         free_problem(ctx);
     }
   } guard{ctx};
-  // PDH_TRACE_SETUP=1 (diagnostics): wall time of the phases of this call on stderr
-  static const bool trace = getenv("PDH_TRACE_SETUP") != nullptr;
+  // the diagnostic switches as they stand now, for all of this set-up; PDH_TRACE_SETUP=1: wall time of its phases on stderr
+  const PlanSwitches sw = read_plan_switches();
   auto t_last = std::chrono::steady_clock::now();
   auto lap = [&](const char *what) {
-    if (!trace)
+    if (!sw.trace)
       return;
     const auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "[pdh_set_problem] %-32s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
@@ -502,7 +514,7 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   Packed &K = *K_owner;
   PDH_TRY(pack_problem(ctx->err, p, row_begin, row_end, K, ctx->exchange_mode, cart));
   lap("validate + repack (host)");
-  auto plan = std::make_unique<KernelPlan>(plan_kernels(p, K, read_plan_switches()));
+  auto plan = std::make_unique<KernelPlan>(plan_kernels(p, K, sw));
   lap("row kernel plan (host)");
   if (cart && plan->kernel != RowKernel::terms)
     return fail(ctx, PDH_EUNSUPPORTED, "cartesian description: the term kernels do not apply (a polytope's tables exceed their LDS budget, "
@@ -512,9 +524,11 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   record_problem(ctx, p, K);
   lap("upload: state of every kernel");
   // 3. device: the state of the row kernel the plan chose, of that one only
+  int cus = 256; // (sizes the MULTI scratch and the row kernel's grid)
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
   if (plan->kernel == RowKernel::rows)
     {
-      PDH_TRY(upload_rows_state(ctx, K, *plan));
+      PDH_TRY(upload_rows_state(ctx, K, *plan, cus));
       lap("upload: pdh_rows.h state");
     }
   else if (plan->kernel == RowKernel::terms)
@@ -523,6 +537,8 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
       lap("upload: term kernel state");
     }
   ctx->prob.row_kernel = plan->kernel;
+  // 4. the launches of every form of the problem
+  resolve_launches(ctx, K, sw, cus);
   ctx->prob.resident = true;
   ctx->ev_used = 0;
   guard.done = true;
@@ -586,8 +602,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
   PDH_TRY(need_problem(ctx, "pdh_assemble_device"));
   ++ctx->values_gen;
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  pdh_launch_fn fn = ctx->prob.tiled ? nullptr : g_launch[ctx->prob.group];
-  const int dim = ctx->prob.dev.dim, n1d = ctx->prob.dev.n1d, nt = ctx->prob.NT, lb = ctx->prob.LB;
+  pdh_ctx::Problem &pr = ctx->prob;
   if (ctx->algorithm == PDH_ALG_MOMENT && !ctx->prob.d_mtab)
     return fail(ctx, PDH_EUNSUPPORTED, "the moment form exists for 3-D bases of degree 1..3 only");
   if (ctx->algorithm == PDH_ALG_ROWS && ctx->prob.row_kernel == RowKernel::none)
@@ -600,10 +615,10 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
           PDH_TRY(take_events(ctx, ev));
           PDH_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
         }
-      if (ctx->prob.row_kernel == RowKernel::terms)
-        PDH_HIP(ctx, pdh_launch_terms(&ctx->prob.dev, &ctx->prob.terms, ctx->prob.n_owned, ctx->stream));
+      if (pr.row_kernel == RowKernel::terms)
+        PDH_HIP(ctx, pdh_launch_terms(&pr.row, &pr.dev, &pr.terms, pr.n_owned, ctx->stream));
       else
-        PDH_HIP(ctx, pdh_launch_rows(&ctx->prob.dev, &ctx->prob.rows, ctx->prob.d_mtab, ctx->prob.n_owned, ctx->stream));
+        PDH_HIP(ctx, pdh_launch_rows(&pr.row, pr.row_zero_sched, &pr.dev, &pr.rows, pr.d_mtab, pr.n_owned, ctx->stream));
       if (ctx->profiling)
         {
           PDH_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
@@ -658,6 +673,15 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
     if (g)
       (void)hipGraphDestroy(g);
   };
+  // k = 0 own blocks, 1 coupling blocks, in the form the algorithm selects
+  auto launch_blocks = [&](int k, int count, hipStream_t s) {
+    if (ctx->use_moment(k))
+      return pdh_launch_moment(&pr.moment[k], &pr.dev, pr.d_mtab, count, s);
+    if (!pr.tiled)
+      return pdh_launch_direct(&pr.direct[k], &pr.dev, count, s);
+    const hipError_t e = pdh_launch_tiled(&pr.direct[k], &pr.dev, count, s);
+    return k == 0 && e == hipSuccess ? pdh_launch_tiled(&pr.direct[2], &pr.dev, count, s) : e;
+  };
   if (ov)
     {
       PDH_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -667,10 +691,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
   if (ctx->profiling)
     PDH_HIP(ctx, hipEventRecord(e0, sd));
   {
-    const hipError_t le = ctx->use_moment(0) ? pdh_launch_moment(n1d, 0, &ctx->prob.dev, ctx->prob.d_mtab, ctx->prob.n_diag_slots, sd)
-                          : ctx->prob.tiled     ? pdh_launch_tiled(dim, n1d, ctx->prob.dev.reaction_c != 0.0 ? 2 : 0, &ctx->prob.dev, ctx->prob.n_diag_slots, sd)
-                                           : fn(dim, n1d, nt, lb, ctx->prob.dev.reaction_c != 0.0 ? 2 : 0, &ctx->prob.dev, ctx->prob.n_diag_slots,
-                                                ctx->prob.lds_diag, sd);
+    const hipError_t le = launch_blocks(0, pr.n_diag_slots, sd);
     if (le != hipSuccess)
       {
         end_capture(false); // (a stream must not be left in capture mode)
@@ -683,9 +704,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
   if (ctx->profiling)
     PDH_HIP(ctx, hipEventRecord(f0, so));
   {
-    const hipError_t le = ctx->use_moment(1) ? pdh_launch_moment(n1d, 1, &ctx->prob.dev, ctx->prob.d_mtab, ctx->prob.n_items, so)
-                          : ctx->prob.tiled     ? pdh_launch_tiled(dim, n1d, 1, &ctx->prob.dev, ctx->prob.n_items, so)
-                                           : fn(dim, n1d, nt, lb, 1, &ctx->prob.dev, ctx->prob.n_items, ctx->prob.lds_off, so);
+    const hipError_t le = launch_blocks(1, pr.n_items, so);
     if (le != hipSuccess)
       {
         end_capture(false);
@@ -931,7 +950,7 @@ extern "C" int pdh_problem_stats(pdh_ctx *ctx, int64_t *stats)
   stats[3] = ctx->prob.n_ap;
   stats[4] = ctx->prob.n_values;
   stats[5] = ctx->prob.dev.n;
-  stats[6] = (int64_t)ctx->prob.lds_diag;
-  stats[7] = (int64_t)ctx->prob.lds_off;
+  stats[6] = (int64_t)pdh::lds_bytes_diag(ctx->prob.dev.dim, ctx->prob.dev.n1d, ctx->prob.NT);
+  stats[7] = (int64_t)pdh::lds_bytes_offdiag(ctx->prob.dev.dim, ctx->prob.dev.n1d, ctx->prob.NT);
   return PDH_OK;
 }

@@ -1,12 +1,10 @@
 // pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp), not installed: the context
 // behind the opaque pdh_ctx of include/polydeal_hip.h, error reporting, the one device-buffer type, the alloc / upload helpers of
-// set-up and the entry guards.  No kernel header here: a unit that launches includes pdh_launch.h itself.
+// set-up and the entry guards.  No kernel header here: pdh_launch.h brings the kernels' argument structs and the launch records.
 #pragma once
 #include "../../include/polydeal_hip.h"
-#include "pdh_dev.h"
+#include "pdh_launch.h"
 #include "pdh_plan.h"
-#include "pdh_rows_tables.h"
-#include "pdh_terms_tables.h"
 
 #include <hip/hip_runtime.h>
 
@@ -111,10 +109,14 @@ struct pdh_ctx
     bool resident = false;
     std::vector<void *> allocs; // every hipMalloc of set-up (upload / device_buffer); the pointers below point into these
     PdhDev dev{};
-    int n_owned = 0, n_items = 0, NT = 0, LB = 0, group = -1;
-    bool tiled = false; // n > 64 dofs per polytope: pdh_tiled.h instead of the kernels of `group`
+    int n_owned = 0, n_items = 0, NT = 0;
+    bool tiled = false; // n > 64 dofs per polytope: pdh_tiled.h instead of the kernels of pdh_inst.hip
+    // The launches of every form pdh_set_algorithm can ask of this problem, resolved once at set-up (pdh_launch.h): the direct form
+    // ([0] own blocks, [1] coupling blocks, tiled: [2] the tile pairs of the own blocks), the moment form where d_mtab exists, the row
+    // kernel of row_kernel.  pdh_assemble_device selects among them (use_rows, use_moment) and launches.
+    PdhLaunch direct[3] = {}, moment[2] = {}, row = {};
+    bool row_zero_sched = false; // pdh_rows.h, FE_DGQ(3) kind: its work counter is zeroed in front of every launch
     int64_t terms_merge[4] = {0, 0, 0, 0}; // term kernels: cells before / after merging, sub-faces before / after
-    size_t lds_diag = 0, lds_off = 0;
     int64_t n_values = 0, n_vq = 0, n_ap = 0;
     int64_t mfma_diag = 0, mfma_offdiag = 0; // MFMA instructions per launch
     int basis = 0;

@@ -1,22 +1,76 @@
-// pdh_launch.h — the one declaration of every kernel launcher of the library.  Included by pdh_capi.cpp, which calls them,
-// and by every .hip file that defines one: extern "C" links a mismatch silently, this way a changed signature does not compile.
+// pdh_launch.h — the one declaration of every kernel launcher of the library.  Included by the driver units, which call them, and by
+// every .hip file that defines one: extern "C" links a mismatch silently, this way a changed signature does not compile.
+// The assembly kernels are launched in two steps.  pdh_set_problem* RESOLVES every form the resident problem can be asked for - each
+// instantiating unit runs its family's ladder once, takes the address of the instantiation and sizes the grid - into PdhLaunch records;
+// pdh_assemble_device LAUNCHES the records it selects through the unit's typed launch function.  Neither step keeps state of its own:
+// what a resolver needs beyond the problem (the diagnostic switches, the device's CU count) set-up hands to it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pdh_dev.h"
 #include "pdh_rows_tables.h"
 #include "pdh_solve.h"
 #include "pdh_terms_tables.h"
 
+// One resolved launch (host only).  kernel: host stub of the instantiation, NULL where nothing could be resolved (no such instantiation,
+// a grid beyond 2^31 - 1 blocks) - launching that answers hipErrorInvalidValue; grid 0: nothing to do, a successful no-op.
+struct PdhLaunch
+{
+  const void *kernel;
+  unsigned grid, block;
+  size_t lds; // dynamic LDS, bytes
+};
+
+// The parameter list of every instantiation of a family.  A resolver converts each kernel it offers to its family's type and a launch
+// function builds the arguments from that type, so a kernel whose signature changed compiles in neither.
+typedef void (*PdhDirectKernel)(PdhDev, int);                             // pdh_kernels.h: k_diag, k_offdiag
+typedef void (*PdhTiledKernel)(PdhDev, int, int);                         // pdh_tiled.h: k_tdiag, k_toffdiag
+typedef void (*PdhMomentKernel)(PdhDev, const double *, int);             // pdh_moment.h: k_mdiag, k_moffdiag
+typedef void (*PdhRowsKernel)(PdhDev, PdhRows, const double *, int);      // pdh_rows.h: k_rows
+typedef void (*PdhTermsKernel)(PdhDev, PdhTerms, int);                    // pdh_terms.h: k_terms, pdh_terms_wg.h: k_terms_wg
+
+template <class... A>
+inline PdhLaunch pdh_record(void (*kernel)(A...), long long grid, unsigned block, size_t lds)
+{
+  return grid > 0x7fffffffLL ? PdhLaunch{} : PdhLaunch{(const void *)kernel, (unsigned)(grid > 0 ? grid : 0), block, lds};
+}
+template <class... A>
+inline hipError_t pdh_launch_as(void (*)(A...), const PdhLaunch &L, hipStream_t stream, A... a)
+{
+  if (!L.kernel)
+    return hipErrorInvalidValue;
+  if (!L.grid)
+    return hipSuccess;
+  void *args[] = {&a...};
+  (void)hipLaunchKernel(L.kernel, dim3(L.grid), dim3(L.block), args, L.lds, stream);
+  return hipGetLastError();
+}
+// f(std::bool_constant<b>{}...) for run-time bools: a family's ladder over its bool template arguments, written once
+template <class F>
+inline void pdh_for_bools(F &&f)
+{
+  f();
+}
+template <class F, class... B>
+inline void pdh_for_bools(F &&f, bool b, B... rest)
+{
+  if (b)
+    pdh_for_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    pdh_for_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 extern "C" {
-// pdh_inst.hip, one translation unit per group of pdh_combos.h: which = 0 diagonal blocks, 1 coupling blocks, 2 diagonal blocks
-// with reaction term
-typedef hipError_t (*pdh_launch_fn)(int dim, int n1d, int nt, int lb, int which, const PdhDev *P, int count, size_t lds,
-                                    hipStream_t stream);
-#define PDH_DECL(g) hipError_t pdh_launch_g##g(int, int, int, int, int, const PdhDev *, int, size_t, hipStream_t);
+// pdh_inst.hip, one translation unit per group of pdh_combos.h: L[0] own blocks (reaction: with reaction term), L[1] coupling blocks; the
+// launch function is the same for every group (pdh_tiled.hip, next to that of the tiled form)
+typedef void (*pdh_resolve_fn)(int dim, int n1d, int nt, int lb, bool reaction, int n_own, int n_items, PdhLaunch *L);
+#define PDH_DECL(g) void pdh_resolve_g##g(int, int, int, int, bool, int, int, PdhLaunch *);
 PDH_DECL(0) PDH_DECL(1) PDH_DECL(2) PDH_DECL(3) PDH_DECL(4) PDH_DECL(5) PDH_DECL(6) PDH_DECL(7)
 #undef PDH_DECL
+hipError_t pdh_launch_direct(const PdhLaunch *L, const PdhDev *P, int count, hipStream_t stream);
 
 // pdh_rhs.hip
 hipError_t pdh_launch_rhs(int dim, int n1d, const PdhDev *P, int count, const double *f_vol, const double *g_face, double *rhs,
@@ -31,16 +85,26 @@ hipError_t pdh_launch_eval_err(int dim, int n1d, const PdhDev *P, int count, con
                                const double *pts, int64_t pts_stride, const double *w, const double *exact_u, const double *exact_g,
                                double *err, hipStream_t stream);
 
-// pdh_moment.hip: the moment form (which = 0 diagonal blocks, 1 coupling blocks) and the kinds of pdh_rows.h
-hipError_t pdh_launch_moment(int n1d, int which, const PdhDev *P, const double *mtab, int count, hipStream_t stream);
-hipError_t pdh_launch_rows(const PdhDev *P, const PdhRows *R, const double *mtab, int count, hipStream_t stream);
+// pdh_moment.hip: the moment form (L[0] diagonal, L[1] coupling blocks) and the kinds of pdh_rows.h.  The row kernel's grid
+// is min(count, cus x waves per CU), the waves per CU the smaller of what fits by LDS and the occupancy query unless waves_per_cu > 0
+// says otherwise; lds_pad: extra dynamic LDS, bytes (PlanSwitches); verbose: one line on stderr
+void pdh_resolve_moment(int n1d, int n, int n_own, int n_items, PdhLaunch *L);
+hipError_t pdh_launch_moment(const PdhLaunch *L, const PdhDev *P, const double *mtab, int count, hipStream_t stream);
+// zero_sched (resolved with the kind): PdhRows::sched is zeroed, stream-ordered, in front of every launch
+PdhLaunch pdh_resolve_rows(const PdhDev *P, const PdhRows *R, int count, int cus, int waves_per_cu, size_t lds_pad, bool verbose,
+                           bool *zero_sched);
+hipError_t pdh_launch_rows(const PdhLaunch *L, bool zero_sched, const PdhDev *P, const PdhRows *R, const double *mtab, int count,
+                           hipStream_t stream);
 
-// pdh_terms.hip
-hipError_t pdh_launch_terms(const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream);
+// pdh_terms.hip; wg_waves: waves of a workgroup of the FE_DGQ(3) kernel, 4 | 8
+PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int wg_waves);
+hipError_t pdh_launch_terms(const PdhLaunch *L, const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream);
 hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T, double *out, int count, hipStream_t stream);
 
-// pdh_tiled.hip: which = 0 own blocks, 2 own blocks with reaction term, 1 coupling blocks
-hipError_t pdh_launch_tiled(int dim, int n1d, int which, const PdhDev *P, int count, hipStream_t stream);
+// pdh_tiled.hip: L[0] own blocks, symmetric tiles ti == tj, L[1] coupling blocks, L[2] own blocks, pairs ti < tj (none of the own
+// blocks resolves if one of the two grids is too large)
+void pdh_resolve_tiled(int dim, int n1d, int n, bool reaction, int n_own, int n_items, PdhLaunch *L);
+hipError_t pdh_launch_tiled(const PdhLaunch *L, const PdhDev *P, int count, hipStream_t stream);
 
 // pdh_cartgen.hip
 hipError_t pdh_launch_gen_volume(int nq, const double *nodes, const double *weights, const double *d_box, const int32_t *d_gcell,

@@ -1,5 +1,4 @@
-// pdh_terms.hip — instantiations and launcher of the term kernel (pdh_terms.h): 3-D FE_DGQ(1,2), FE_AggloDGP(1..3).
-#include <cstdlib>
+// pdh_terms.hip — instantiations, resolver and launcher of the term kernel (pdh_terms.h): 3-D FE_DGQ(1,2), FE_AggloDGP(1..3).
 #include "pdh_terms.h"
 #include "pdh_terms_wg.h"
 #include "pdh_launch.h"
@@ -21,69 +20,37 @@ extern "C" hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T
   return hipGetLastError();
 }
 
-extern "C" hipError_t pdh_launch_terms(const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream)
+// one workgroup per owned polytope: of one wave (pdh_terms.h), FE_DGQ(3) of wg_waves = 4 | 8 waves (pdh_terms_wg.h; PDH_TERMS_WG_WAVES,
+// diagnostics).  Rules of up to 4 / up to 8 points per direction (PdhTerms::task_pts) have their own instantiations.
+extern "C" PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int wg_waves)
 {
-  if (count <= 0)
-    return hipSuccess;
-  const int full = P->n1d * P->n1d * P->n1d;
-  const int basis = P->n == full ? 0 : 1;
-  hipError_t rc = hipErrorInvalidValue;
+  PdhLaunch L{};
+  const int basis = P->n == P->n1d * P->n1d * P->n1d ? 0 : 1;
+  const bool shifted = P->diag_first != 0, small = T->task_pts <= 4;
   if (P->n1d == 4 && basis == 0)
-    {
-      // FE_DGQ(3): a workgroup of W waves per polytope (pdh_terms_wg.h); PDH_TERMS_WG_WAVES = 4 | 8 (diagnostics)
-      static const int waves = [] {
-        const char *e = getenv("PDH_TERMS_WG_WAVES");
-        const int w = e ? atoi(e) : 4;
-        return w == 8 ? 8 : 4;
-      }();
-      const size_t lds = (size_t)T->lds_bytes;
-      const bool small = T->task_pts <= 4;
-      auto go = [&](auto w_, auto shifted_, auto pmax_) {
-        constexpr int W = decltype(w_)::value;
-        hipLaunchKernelGGL((pdht::k_terms_wg<W, decltype(shifted_)::value, decltype(pmax_)::value>), dim3((unsigned)count), dim3(PDH_WAVE * W),
-                           lds, stream, *P, *T, count);
-      };
-      using std::integral_constant;
-      auto go_w = [&](auto w_) {
-        if (P->diag_first && small)
-          go(w_, std::true_type{}, integral_constant<int, 4>{});
-        else if (P->diag_first)
-          go(w_, std::true_type{}, integral_constant<int, 8>{});
-        else if (small)
-          go(w_, std::false_type{}, integral_constant<int, 4>{});
-        else
-          go(w_, std::false_type{}, integral_constant<int, 8>{});
-      };
-      if (waves == 8)
-        go_w(integral_constant<int, 8>{});
-      else
-        go_w(integral_constant<int, 4>{});
-      return hipGetLastError();
-    }
-  for_kind(P->n1d, basis, [&](auto n_, auto b_) {
-    constexpr int N = decltype(n_)::value, B = decltype(b_)::value;
-    if (P->n != pdht::Kind<N, B>::NF)
-      return;
-    const size_t lds = (size_t)T->lds_bytes;
-    const bool small = T->task_pts <= 4; // (rules of up to 4 / up to 8 points per direction)
-    auto go = [&](auto shifted_, auto pmax_) {
-      constexpr bool S = decltype(shifted_)::value;
-      constexpr int PM = decltype(pmax_)::value;
-      if (T->split)
-        hipLaunchKernelGGL((pdht::k_terms<N, B, S, PM, true>), dim3((unsigned)count), dim3(PDH_WAVE), lds, stream, *P, *T, count);
-      else
-        hipLaunchKernelGGL((pdht::k_terms<N, B, S, PM, false>), dim3((unsigned)count), dim3(PDH_WAVE), lds, stream, *P, *T, count);
-    };
-    using std::integral_constant;
-    if (P->diag_first && small)
-      go(std::true_type{}, integral_constant<int, 4>{});
-    else if (P->diag_first)
-      go(std::true_type{}, integral_constant<int, 8>{});
-    else if (small)
-      go(std::false_type{}, integral_constant<int, 4>{});
-    else
-      go(std::false_type{}, integral_constant<int, 8>{});
-    rc = hipGetLastError();
-  });
-  return rc;
+    pdh_for_bools(
+      [&](auto eight_, auto shifted_, auto small_) {
+        constexpr int W = decltype(eight_)::value ? 8 : 4, PM = decltype(small_)::value ? 4 : 8;
+        const PdhTermsKernel k = pdht::k_terms_wg<W, decltype(shifted_)::value, PM>;
+        L = pdh_record(k, count, PDH_WAVE * W, (size_t)T->lds_bytes);
+      },
+      wg_waves == 8, shifted, small);
+  else
+    for_kind(P->n1d, basis, [&](auto n_, auto b_) {
+      constexpr int N = decltype(n_)::value, B = decltype(b_)::value;
+      if (P->n != pdht::Kind<N, B>::NF)
+        return;
+      pdh_for_bools(
+        [&](auto shifted_, auto small_, auto split_) {
+          constexpr int PM = decltype(small_)::value ? 4 : 8;
+          const PdhTermsKernel k = pdht::k_terms<N, B, decltype(shifted_)::value, PM, decltype(split_)::value>;
+          L = pdh_record(k, count, PDH_WAVE, (size_t)T->lds_bytes);
+        },
+        shifted, small, T->split != 0);
+    });
+  return L;
+}
+extern "C" hipError_t pdh_launch_terms(const PdhLaunch *L, const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream)
+{
+  return pdh_launch_as(PdhTermsKernel(), *L, stream, *P, *T, count);
 }

@@ -135,7 +135,7 @@ def test_dgq3_on_box_meshes(mesh, vname, diag_first):
 
 
 def test_dgq3_workgroup_kernel_eight_waves():
-    """k_terms_wg with eight waves per polytope (PDH_TERMS_WG_WAVES is read once per process: a child process of its own)."""
+    """k_terms_wg with eight waves per polytope (PDH_TERMS_WG_WAVES was read once per process, now at every set-up: still a child process of its own)."""
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gpu_anisotropic as t; "
             "[t._dgq3_auto(*c) for c in t.SMALL_MESHES]; print('ok')" % (ROOT, HERE))
     env = dict(os.environ, PDH_TERMS_WG_WAVES="8")

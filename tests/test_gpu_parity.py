@@ -1491,7 +1491,7 @@ def test_term_kernel_workgroup_form_for_dgq3(kind, cells, per, vname, diag_first
     import subprocess
     import sys
 
-    # (the number of waves is read once per process by the launcher: one child process per value)
+    # (the number of waves was once read once per process; it is read at every set-up now: the child process per value stays)
     if waves != "4":
         here = __import__('os').path.dirname(__import__('os').path.abspath(__file__))
         code = ("import os, sys; os.environ['PDH_TERMS_WG_WAVES'] = %r; sys.path.insert(0, %r); sys.path.insert(0, %r); "
@@ -1651,6 +1651,62 @@ def test_small_problem_graph_replay_is_transparent():
             got = ctx.assemble()
             assert_parity_ah(got, ref3, ah3, what=alg)
     ctx.close()
+
+
+_DGQ3_CUBE = []
+
+
+def dgq3_cube():
+    """FE_DGQ(3) on 4^3 Cartesian cells in blocks of 2, tensor rules: handler, flattened input and the oracle's values, made once"""
+    if not _DGQ3_CUBE:
+        fe = po.FE_DGQ(3, 3)
+        ah = build(3, 2, 2, fe, 4)
+        var = po.variant_poisson_example(fe)
+        _DGQ3_CUBE.extend((ah, flatten(ah, var), po.assemble_csr(ah, var)[2]))
+    return _DGQ3_CUBE
+
+
+def test_algorithm_changes_on_one_resident_problem():
+    """Set-up resolves the launches of every form pdh_set_algorithm can ask of the resident problem - direct pair, moment pair and the
+    row kernel side by side: cycling through them on ONE set_problem gives the oracle's matrix every time."""
+    import polydeal_amd as pa
+
+    ah, kw, ref = dgq3_cube()
+    ctx = pa.Context(0)
+    ctx.set_problem(pa.Problem(**kw))
+    for alg, used, kern in (("auto", "rows", "terms"), ("direct", "direct", "none"), ("moment", "moment", "none"),
+                            ("rows", "rows", "terms"), ("auto", "rows", "terms")):
+        ctx.set_algorithm(alg)
+        assert (ctx.algorithm_in_use(), ctx.rows_kernel_in_use()) == (used, kern), alg
+        for _ in range(2):
+            assert_parity_ah(ctx.assemble(), ref, ah, what=alg)
+    ctx.close()
+
+
+def test_row_kernel_switches_follow_the_problem(monkeypatch, capfd):
+    """PDH_ROWS_WAVES_PER_CU is read at every pdh_set_problem and holds for that resident problem, not for the process: two set-ups on
+    one context report 1 and then 2 waves per CU (one line of PDH_ROWS_VERBOSE per set-up that takes the row kernel) and assemble the
+    same bits."""
+    import re
+
+    import polydeal_amd as pa
+
+    ah, kw, ref = dgq3_cube()
+    monkeypatch.setenv("PDH_TERMS_DGQ3", "0")
+    monkeypatch.setenv("PDH_ROWS_VERBOSE", "1")
+    ctx = pa.Context(0)
+    got = []
+    for waves in ("1", "2"):
+        monkeypatch.setenv("PDH_ROWS_WAVES_PER_CU", waves)
+        ctx.set_problem(pa.Problem(**kw))
+        assert ctx.rows_kernel_in_use() == "pieces"
+        got.append(ctx.assemble())
+        assert_parity_ah(got[-1], ref, ah, what="%s waves per CU" % waves)
+    ctx.close()
+    lines = [l for l in capfd.readouterr().err.splitlines() if l.startswith("k_rows<")]
+    print("\n".join(lines))
+    assert [re.search(r"(\d+) taken", l).group(1) for l in lines] == ["1", "2"], lines
+    assert np.array_equal(got[0], got[1])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
