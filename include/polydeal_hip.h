@@ -409,6 +409,57 @@ int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double *d_x, int 
  * offdiag [k-1] (not read for k = 1), 1 <= k <= 256, by bisection on Sturm counts (a few ulp of the largest |eigenvalue|). */
 int pdh_tridiagonal_eigenvalues(int k, const double *diag, const double *offdiag, double *lo, double *hi);
 
+/* r = b - A x on the resident values: the one vector operation of a multigrid cycle next to the smoother, the transfers below and the
+ * coarse solve.  Device pointers, asynchronous on pdh_stream(); x [n_rows] in the global numbering like pdh_vmult_device, b and r
+ * [row_end-row_begin].  r must overlap neither x nor b (PDH_EINVAL); PDH_ESTATE without a resident problem.                      */
+int pdh_residual_device(pdh_ctx *ctx, const double *d_b, const double *d_x, double *d_r);
+
+/* Level transfer between two NESTED polytopal FE_DGQ spaces (pdh_transfer.hip): the reference's MGTransferAgglomeration
+ * (include/multigrid_amg.h:439-490 prolongate, prolongate_and_add, restrict_and_add) over the injection of Utils::fill_injection_matrix
+ * (include/utils.h:95-270), without its matrix.  The basis lives on the bounding box and the support points of a fine polytope are a
+ * tensor grid in its box, so every injection block (fine polytope F, parent C) is the Kronecker product of `dim` 1-D matrices
+ *   B_c[i][j] = l_j((lo_F[c] + node_i h_F[c] - lo_C[c]) / h_C[c])
+ * (l_j: Lagrange polynomials on the p + 1 Gauss-Lobatto nodes; first axis fastest in the dof index): dim (p+1)^2 doubles per fine
+ * polytope, applied by sum factorisation.  All pointers of the description are caller-owned host memory, read during the call only. */
+typedef struct pdh_transfer_desc
+{
+  int32_t dim, degree, basis;          /* 2|3, 1..7, PDH_BASIS_DGQ                                     */
+  int32_t n_fine, n_coarse;            /* polytopes                                                    */
+  int32_t n_fine_rows, n_coarse_rows;  /* lengths of the level vectors                                 */
+  const double  *fine_bbox, *coarse_bbox;              /* [n][2][dim] as pdh_problem.bbox              */
+  const int32_t *fine_dof_offset, *coarse_dof_offset;  /* [n] as pdh_problem.dof_offset                */
+  const int32_t *parent;                               /* [n_fine] coarse polytope of every fine one   */
+} pdh_transfer_desc;
+/* Host-only.  PDH_EUNSUPPORTED: FE_AggloDGP (no support points; the reference refuses it too, include/fe_agglodgp.h:63), degree 0 or
+ * above 7, 2-D with more than 64 dofs per polytope.  PDH_EINVAL: a parent out of range, a coarse polytope without children, a
+ * degenerate box, a fine box not inside its parent's (slack: 1e-12 of the parent's extent per axis), dof ranges [off, off + n) that
+ * overlap or leave [0, n_rows) on either level, n_coarse >= n_fine (include/utils.h:120).  pdh_last_error(NULL) says which.      */
+int pdh_check_transfer(const pdh_transfer_desc *d);
+/* Host-only: the 1-D matrices, out [n_fine][dim][p+1][p+1] (B_c[i][j] as above), from the tables of the kernels' basis. */
+int pdh_transfer_matrices_1d(const pdh_transfer_desc *d, double *out);
+/* Host-only: the children of every coarse polytope as a CSR, child_ptr [n_coarse+1], child_idx [n_fine], ascending fine index per
+ * parent - the order in which the restriction adds the children's contributions.                                           */
+int pdh_transfer_children(const pdh_transfer_desc *d, int32_t *child_ptr, int32_t *child_idx);
+
+/* A transfer lives on the device and stream of the context it was created on and needs NO resident problem there (the levels live in
+ * different contexts); destroy it before its context.  pdh_transfer_create runs pdh_check_transfer, builds the tables and the children
+ * CSR on the host and uploads them - there is no set-up kernel.  Errors of a transfer are reported on its context (pdh_last_error).
+ *   prolongate          fine    = P coarse        prolongate_and_add    fine   += P coarse
+ *   restrict            coarse  = P^T fine        restrict_and_add      coarse += P^T fine
+ * The _device entries take device pointers (coarse [n_coarse_rows], fine [n_fine_rows]) and are asynchronous on pdh_stream() of the
+ * context; pdh_prolongate / pdh_restrict take host pointers, staged like pdh_vmult, and give the same bits.  NULL or overlapping vectors:
+ * PDH_EINVAL.  The restriction adds the children of a coarse polytope in ascending fine index, no atomics: the same call on the same
+ * data gives the same bits.  Global descriptions only (one context per level, like pdh_solve_cg).                                */
+typedef struct pdh_transfer pdh_transfer;
+int  pdh_transfer_create(pdh_ctx *ctx, const pdh_transfer_desc *d, pdh_transfer **out);
+void pdh_transfer_destroy(pdh_transfer *t);
+int pdh_prolongate_device        (pdh_transfer *t, const double *d_coarse, double *d_fine);
+int pdh_prolongate_and_add_device(pdh_transfer *t, const double *d_coarse, double *d_fine);
+int pdh_restrict_device          (pdh_transfer *t, const double *d_fine,   double *d_coarse);
+int pdh_restrict_and_add_device  (pdh_transfer *t, const double *d_fine,   double *d_coarse);
+int pdh_prolongate(pdh_transfer *t, const double *coarse, double *fine);
+int pdh_restrict  (pdh_transfer *t, const double *fine,   double *coarse);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

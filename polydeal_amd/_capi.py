@@ -47,6 +47,29 @@ class pdh_chebyshev_info(C.Structure):
                 ("degree", C.c_int32), ("inner", C.c_int32)]
 
 
+class _Opaque(C.c_void_p):
+    """A typed opaque handle: accepts None, an address, or any c_void_p holding one."""
+
+    @classmethod
+    def from_param(cls, v):
+        return super().from_param(v.value if isinstance(v, C.c_void_p) and not isinstance(v, cls) else v)
+
+
+class pdh_ctx_p(_Opaque):
+    """pdh_ctx * (the entry points of the level transfers and pdh_residual_device)"""
+
+
+class pdh_transfer_p(_Opaque):
+    """pdh_transfer *"""
+
+
+class pdh_transfer_desc(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("degree", C.c_int32), ("basis", C.c_int32), ("n_fine", C.c_int32), ("n_coarse", C.c_int32),
+                ("n_fine_rows", C.c_int32), ("n_coarse_rows", C.c_int32),
+                ("fine_bbox", C.c_void_p), ("coarse_bbox", C.c_void_p), ("fine_dof_offset", C.c_void_p),
+                ("coarse_dof_offset", C.c_void_p), ("parent", C.c_void_p)]
+
+
 class pdh_problem(C.Structure):
     _fields_ = [
         ("dim", C.c_int32), ("degree", C.c_int32), ("basis", C.c_int32), ("n_agg", C.c_int32),
@@ -74,8 +97,13 @@ EXPORTS = [
     "pdh_global_error", "pdh_global_error_device", "pdh_rows_kernel_in_use", "pdh_check_terms", "pdh_terms_merge_stats", "pdh_set_problem_cartesian",
     "pdh_vmult", "pdh_vmult_device", "pdh_setup_preconditioner", "pdh_precondition_device", "pdh_solve_cg", "pdh_solve_cg_device",
     "pdh_setup_chebyshev", "pdh_chebyshev_step_device", "pdh_tridiagonal_eigenvalues",
+    "pdh_residual_device", "pdh_check_transfer", "pdh_transfer_children", "pdh_transfer_create",
+    "pdh_transfer_destroy", "pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device",
+    "pdh_restrict_and_add_device", "pdh_prolongate", "pdh_restrict",
 ]
 
+# (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
+# include/polydeal_hip.h that consist of letters and underscores)
 _lib = None
 
 
@@ -153,6 +181,16 @@ def _bind(lib):
     lib.pdh_setup_chebyshev.argtypes = [C.c_void_p, P(pdh_chebyshev_control), P(pdh_chebyshev_info)]
     lib.pdh_chebyshev_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pdh_tridiagonal_eigenvalues.argtypes = [C.c_int, C.c_void_p, C.c_void_p, P(C.c_double), P(C.c_double)]
+    lib.pdh_residual_device.argtypes = [pdh_ctx_p] + [C.c_void_p] * 3
+    lib.pdh_check_transfer.argtypes = [P(pdh_transfer_desc)]
+    lib.pdh_transfer_matrices_1d.argtypes = [P(pdh_transfer_desc), C.c_void_p]
+    lib.pdh_transfer_children.argtypes = [P(pdh_transfer_desc), C.c_void_p, C.c_void_p]
+    lib.pdh_transfer_create.argtypes = [pdh_ctx_p, P(pdh_transfer_desc), P(C.c_void_p)]
+    lib.pdh_transfer_destroy.argtypes = [pdh_transfer_p]
+    lib.pdh_transfer_destroy.restype = None
+    for name in ("pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device", "pdh_restrict_and_add_device",
+                 "pdh_prolongate", "pdh_restrict"):
+        getattr(lib, name).argtypes = [pdh_transfer_p, C.c_void_p, C.c_void_p]
     return real
 
 
@@ -226,6 +264,109 @@ class Problem:
         if rc != PDH_OK:
             raise PdhError(rc, lib.pdh_last_error(None).decode())
         return list(stats)
+
+
+class TransferDesc:
+    """Owns the NumPy arrays behind a pdh_transfer_desc (two nested FE_DGQ levels: boxes [n][2][dim], first dof of every polytope,
+    parent of every fine polytope)."""
+
+    def __init__(self, *, dim, degree, fine_bbox, coarse_bbox, fine_dof_offset, coarse_dof_offset, parent, n_fine_rows=None,
+                 n_coarse_rows=None, basis=PDH_BASIS_DGQ):
+        self.fine_bbox = np.ascontiguousarray(fine_bbox, dtype=np.float64).reshape(-1, 2, dim)
+        self.coarse_bbox = np.ascontiguousarray(coarse_bbox, dtype=np.float64).reshape(-1, 2, dim)
+        self.fine_dof_offset = np.ascontiguousarray(fine_dof_offset, dtype=np.int32)
+        self.coarse_dof_offset = np.ascontiguousarray(coarse_dof_offset, dtype=np.int32)
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32)
+        self.dim, self.degree, self.basis = int(dim), int(degree), int(basis)
+        self.n = (self.degree + 1) ** self.dim
+        self.n_fine, self.n_coarse = len(self.fine_bbox), len(self.coarse_bbox)
+        if self.fine_dof_offset.shape != (self.n_fine,) or self.parent.shape != (self.n_fine,) or \
+                self.coarse_dof_offset.shape != (self.n_coarse,):
+            raise ValueError("fine_dof_offset / parent [n_fine] and coarse_dof_offset [n_coarse]")
+        self.n_fine_rows = self.n_fine * self.n if n_fine_rows is None else int(n_fine_rows)
+        self.n_coarse_rows = self.n_coarse * self.n if n_coarse_rows is None else int(n_coarse_rows)
+        self.c = pdh_transfer_desc(self.dim, self.degree, self.basis, self.n_fine, self.n_coarse, self.n_fine_rows, self.n_coarse_rows,
+                                   self.fine_bbox.ctypes.data, self.coarse_bbox.ctypes.data, self.fine_dof_offset.ctypes.data,
+                                   self.coarse_dof_offset.ctypes.data, self.parent.ctypes.data)
+
+    @staticmethod
+    def _chk(rc):
+        if rc != PDH_OK:
+            raise PdhError(rc, load_library().pdh_last_error(None).decode())
+
+    def check(self):
+        """pdh_check_transfer: host only, no GPU."""
+        self._chk(load_library().pdh_check_transfer(C.byref(self.c)))
+
+    def matrices_1d(self):
+        """[n_fine][dim][p+1][p+1]: B_c[i][j], the 1-D factors of every injection block (host only)."""
+        out = np.empty((self.n_fine, self.dim, self.degree + 1, self.degree + 1))
+        self._chk(load_library().pdh_transfer_matrices_1d(C.byref(self.c), out.ctypes.data))
+        return out
+
+    def children(self):
+        """(child_ptr [n_coarse+1], child_idx [n_fine]): the summation order of the restriction (host only)."""
+        ptr, idx = np.empty(self.n_coarse + 1, dtype=np.int32), np.empty(self.n_fine, dtype=np.int32)
+        self._chk(load_library().pdh_transfer_children(C.byref(self.c), ptr.ctypes.data, idx.ctypes.data))
+        return ptr, idx
+
+
+class Transfer:
+    """pdh_transfer wrapper: prolongation / restriction between two nested levels on the device and stream of `ctx`, which needs no
+    resident problem.  Close it before its context."""
+
+    def __init__(self, ctx, desc: TransferDesc):
+        self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
+        h = C.c_void_p()
+        ctx._chk(self.lib.pdh_transfer_create(ctx.h, C.byref(desc.c), C.byref(h)))
+        self.h = h
+
+    def _dev(self, fn, d_src, d_dst):
+        self.ctx._chk(fn(self.h, C.c_void_p(d_src), C.c_void_p(d_dst)))
+
+    def prolongate_device(self, d_coarse, d_fine):
+        """fine = P coarse; device pointers (ints), asynchronous on the context's stream."""
+        self._dev(self.lib.pdh_prolongate_device, d_coarse, d_fine)
+
+    def prolongate_and_add_device(self, d_coarse, d_fine):
+        """fine += P coarse"""
+        self._dev(self.lib.pdh_prolongate_and_add_device, d_coarse, d_fine)
+
+    def restrict_device(self, d_fine, d_coarse):
+        """coarse = P^T fine"""
+        self._dev(self.lib.pdh_restrict_device, d_fine, d_coarse)
+
+    def restrict_and_add_device(self, d_fine, d_coarse):
+        """coarse += P^T fine"""
+        self._dev(self.lib.pdh_restrict_and_add_device, d_fine, d_coarse)
+
+    def _host(self, fn, src, n_src, n_dst):
+        a = np.ascontiguousarray(src, dtype=np.float64)
+        if a.shape != (n_src,):
+            raise ValueError("the source vector must have %d entries" % n_src)
+        out = np.empty(n_dst)
+        self.ctx._chk(fn(self.h, C.c_void_p(a.ctypes.data), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def prolongate(self, coarse):
+        """P coarse for a host array"""
+        return self._host(self.lib.pdh_prolongate, coarse, self.desc.n_coarse_rows, self.desc.n_fine_rows)
+
+    def restrict(self, fine):
+        """P^T fine for a host array"""
+        return self._host(self.lib.pdh_restrict, fine, self.desc.n_fine_rows, self.desc.n_coarse_rows)
+
+    def close(self):
+        if self.h:
+            self.lib.pdh_transfer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.ctx.h:  # a context closed first took the device with it: nothing to free through
+                self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -379,6 +520,10 @@ class Context:
     def vmult_device(self, d_x, d_y):
         """Device pointers (ints); asynchronous on the context's stream."""
         self._chk(self.lib.pdh_vmult_device(self.h, C.c_void_p(d_x), C.c_void_p(d_y)))
+
+    def residual_device(self, d_b, d_x, d_r):
+        """r = b - A x on the resident values; device pointers (ints), asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_residual_device(self.h, C.c_void_p(d_b), C.c_void_p(d_x), C.c_void_p(d_r)))
 
     def setup_preconditioner(self, kind):
         """'none' | 'jacobi' | 'block_jacobi' (or PDH_PREC_*), built from the values as they stand."""

@@ -1685,37 +1685,47 @@ inline pdh_chebyshev_info setup_chebyshev(pdh_ctx *ctx, int inner = PDH_PREC_BLO
 
 namespace Utils
 {
+// Parent of every fine polytope in a pair of nested handlers, shared by fill_injection_matrix and MGTransferAgglomeration.  The reference
+// takes polytope->children() from the R-tree hierarchy; here the parent of F is the coarse polytope that holds F's cells (the two handlers
+// must be nested over the same grid, checked).  Needs support points, i.e. FE_DGQ (FE_AggloDGP has none: reference
+// include/fe_agglodgp.h:63).
+inline std::vector<int> nested_parents(const AgglomerationHandler &coarse_ah, const AgglomerationHandler &fine_ah, const char *who)
+{
+  const FiniteElement &fe = coarse_ah.get_fe();
+  if (fe.basis != PDH_BASIS_DGQ || fine_ah.get_fe().basis != fe.basis || fine_ah.get_fe().degree != fe.degree)
+    throw std::invalid_argument(std::string(who) + " needs the same FE_DGQ space on both handlers");
+  if (&coarse_ah.get_triangulation() != &fine_ah.get_triangulation())
+    throw std::invalid_argument("both handlers must live on the same grid");
+  if (!(coarse_ah.n_dofs() < fine_ah.n_dofs()))
+    throw std::invalid_argument("the coarse space must be smaller than the fine one"); // utils.h:120
+  const int nF = (int)fine_ah.n_agglomerates();
+  std::vector<int> parent(nF);
+  for (int F = 0; F < nF; ++F)
+    {
+      parent[F] = coarse_ah.cell_to_polytope_index(fine_ah.master_index(F));
+      for (int cell : fine_ah.get_agglomerate(F)) // all its cells must share it
+        if (coarse_ah.cell_to_polytope_index(cell) != parent[F])
+          throw std::invalid_argument("fine polytopes are not nested in the coarse ones");
+    }
+  return parent;
+}
+
 // Utils::fill_injection_matrix (reference include/utils.h:95-270): the injection from the coarse polytopal
 // space into the fine one, row block of fine polytope F / column block of its parent C:
 //   local_matrix(i, j) = phi^C_j( coarse_bbox.real_to_unit( fine_bbox.unit_to_real(support point i) ) ).
-// The reference takes polytope->children() from the R-tree hierarchy; here the children of C are the fine
-// polytopes whose cells lie in C (the two handlers must be nested over the same grid, checked).  Needs support
-// points, i.e. FE_DGQ (FE_AggloDGP has none: reference include/fe_agglodgp.h:63).  The basis evaluation runs on
+// The children of C are the fine polytopes whose cells lie in C (nested_parents).  The basis evaluation runs on
 // the device (pdh_shape_values); output is CSR over fine rows x coarse columns, n entries per row.
 inline void fill_injection_matrix(const AgglomerationHandler &coarse_ah, const AgglomerationHandler &fine_ah,
                                   std::vector<int64_t> &rowptr, std::vector<int32_t> &colind, std::vector<double> &values,
                                   int device = 0)
 {
+  const std::vector<int> parent = nested_parents(coarse_ah, fine_ah, "fill_injection_matrix");
   const FiniteElement &fe = coarse_ah.get_fe();
-  if (fe.basis != PDH_BASIS_DGQ || fine_ah.get_fe().basis != fe.basis || fine_ah.get_fe().degree != fe.degree)
-    throw std::invalid_argument("fill_injection_matrix needs the same FE_DGQ space on both handlers");
-  if (&coarse_ah.get_triangulation() != &fine_ah.get_triangulation())
-    throw std::invalid_argument("both handlers must live on the same grid");
-  if (!(coarse_ah.n_dofs() < fine_ah.n_dofs()))
-    throw std::invalid_argument("the coarse space must be smaller than the fine one"); // utils.h:120
-  const int dim = fe.dim, n = fe.n_dofs_per_cell(), n1d = fe.degree + 1;
+  const int dim = fe.dim, n = fe.n_dofs_per_cell();
   const int nC = (int)coarse_ah.n_agglomerates(), nF = (int)fine_ah.n_agglomerates();
-  // parent of every fine polytope; all its cells must share it
-  std::vector<int> parent(nF);
   std::vector<std::vector<int>> children(nC);
   for (int F = 0; F < nF; ++F)
-    {
-      parent[F] = coarse_ah.cell_to_polytope_index(fine_ah.master_index(F));
-      for (int cell : fine_ah.get_agglomerate(F))
-        if (coarse_ah.cell_to_polytope_index(cell) != parent[F])
-          throw std::invalid_argument("fine polytopes are not nested in the coarse ones");
-      children[parent[F]].push_back(F);
-    }
+    children[parent[F]].push_back(F);
   // unit support points: tensor Gauss-Lobatto nodes, lexicographic [deal.II FE_DGQ]
   const auto nodes = pdh::gauss_lobatto_nodes(fe.degree);
   const auto mi = pdh::multi_indices(dim, fe.degree, fe.basis);
@@ -1745,7 +1755,6 @@ inline void fill_injection_matrix(const AgglomerationHandler &coarse_ah, const A
             row_of_point[q] = fine_ah.dof_offset_of(F) + i;
           }
     }
-  (void)n1d;
   std::vector<double> local((size_t)N * n);
   pdh_ctx *ctx = nullptr;
   if (pdh_create(&ctx, device) != PDH_OK)
@@ -1770,5 +1779,115 @@ inline void fill_injection_matrix(const AgglomerationHandler &coarse_ah, const A
           values[(size_t)row_of_point[q] * n + j] = local[(size_t)q * n + j];
         }
 }
+
+// The pdh_transfer_desc of a pair of nested handlers (global descriptions): owns the arrays `c` points to.
+struct TransferDescription
+{
+  std::vector<double> fine_bbox, coarse_bbox;
+  std::vector<int32_t> fine_dof_offset, coarse_dof_offset, parent;
+  pdh_transfer_desc c{};
+  TransferDescription(const AgglomerationHandler &coarse_ah, const AgglomerationHandler &fine_ah)
+  {
+    const std::vector<int> par = nested_parents(coarse_ah, fine_ah, "MGTransferAgglomeration");
+    parent.assign(par.begin(), par.end());
+    const int dim = coarse_ah.get_fe().dim;
+    auto level = [dim](const AgglomerationHandler &ah, std::vector<double> &bbox, std::vector<int32_t> &off) {
+      const int nA = (int)ah.n_agglomerates();
+      bbox.resize((size_t)nA * 2 * dim);
+      off.resize((size_t)nA);
+      for (int P = 0; P < nA; ++P)
+        {
+          for (int c = 0; c < dim; ++c)
+            {
+              bbox[(size_t)P * 2 * dim + c] = ah.bbox(P)[c];
+              bbox[(size_t)P * 2 * dim + dim + c] = ah.bbox(P)[3 + c];
+            }
+          off[(size_t)P] = ah.dof_offset_of(P);
+        }
+    };
+    level(fine_ah, fine_bbox, fine_dof_offset);
+    level(coarse_ah, coarse_bbox, coarse_dof_offset);
+    c.dim = dim;
+    c.degree = coarse_ah.get_fe().degree;
+    c.basis = coarse_ah.get_fe().basis;
+    c.n_fine = (int32_t)fine_ah.n_agglomerates();
+    c.n_coarse = (int32_t)coarse_ah.n_agglomerates();
+    c.n_fine_rows = (int32_t)fine_ah.n_dofs();
+    c.n_coarse_rows = (int32_t)coarse_ah.n_dofs();
+    c.fine_bbox = fine_bbox.data();
+    c.coarse_bbox = coarse_bbox.data();
+    c.fine_dof_offset = fine_dof_offset.data();
+    c.coarse_dof_offset = coarse_dof_offset.data();
+    c.parent = parent.data();
+  }
+  TransferDescription(const TransferDescription &) = delete;
+  TransferDescription &operator=(const TransferDescription &) = delete;
+};
+
+// MGTransferAgglomeration (reference include/multigrid_amg.h:439-490) between two nested handlers, applied on the device of `ctx`
+// without the injection matrix (pdh_transfer_create: 1-D factors + sum factorisation).  `ctx` needs no resident problem and must
+// outlive the transfer.  The vector forms take host vectors (dst sized by the call); the *_device forms take device pointers and are
+// asynchronous on pdh_stream(ctx).
+class MGTransferAgglomeration
+{
+public:
+  MGTransferAgglomeration(const AgglomerationHandler &coarse_ah, const AgglomerationHandler &fine_ah, pdh_ctx *ctx)
+    : ctx(ctx), n_fine((size_t)fine_ah.n_dofs()), n_coarse((size_t)coarse_ah.n_dofs())
+  {
+    const TransferDescription T(coarse_ah, fine_ah);
+    if (pdh_transfer_create(ctx, &T.c, &t) != PDH_OK)
+      throw std::runtime_error(std::string("pdh_transfer_create: ") + pdh_last_error(ctx));
+  }
+  ~MGTransferAgglomeration() { pdh_transfer_destroy(t); }
+  MGTransferAgglomeration(const MGTransferAgglomeration &) = delete;
+  MGTransferAgglomeration &operator=(const MGTransferAgglomeration &) = delete;
+
+  void prolongate(std::vector<double> &dst, const std::vector<double> &src) const
+  {
+    need(src.size() == n_coarse, "prolongate: src must have the coarse level's size");
+    dst.resize(n_fine);
+    check(pdh_prolongate(t, src.data(), dst.data()), "pdh_prolongate");
+  }
+  void prolongate_and_add(std::vector<double> &dst, const std::vector<double> &src) const
+  {
+    need(dst.size() == n_fine, "prolongate_and_add: dst must have the fine level's size");
+    std::vector<double> tmp;
+    prolongate(tmp, src);
+    for (size_t i = 0; i < n_fine; ++i)
+      dst[i] += tmp[i];
+  }
+  void restrict_and_add(std::vector<double> &dst, const std::vector<double> &src) const
+  {
+    need(src.size() == n_fine && dst.size() == n_coarse, "restrict_and_add: src / dst must have the fine / coarse level's size");
+    std::vector<double> tmp(n_coarse);
+    check(pdh_restrict(t, src.data(), tmp.data()), "pdh_restrict");
+    for (size_t i = 0; i < n_coarse; ++i)
+      dst[i] += tmp[i];
+  }
+  void prolongate_device(double *d_dst, const double *d_src) const { check(pdh_prolongate_device(t, d_src, d_dst), "pdh_prolongate_device"); }
+  void prolongate_and_add_device(double *d_dst, const double *d_src) const
+  {
+    check(pdh_prolongate_and_add_device(t, d_src, d_dst), "pdh_prolongate_and_add_device");
+  }
+  void restrict_and_add_device(double *d_dst, const double *d_src) const
+  {
+    check(pdh_restrict_and_add_device(t, d_src, d_dst), "pdh_restrict_and_add_device");
+  }
+
+private:
+  static void need(bool ok, const char *msg)
+  {
+    if (!ok)
+      throw std::invalid_argument(std::string("MGTransferAgglomeration::") + msg);
+  }
+  void check(int rc, const char *what) const
+  {
+    if (rc != PDH_OK)
+      throw std::runtime_error(std::string(what) + ": " + pdh_last_error(ctx));
+  }
+  pdh_ctx *ctx;
+  pdh_transfer *t = nullptr;
+  size_t n_fine, n_coarse;
+};
 } // namespace Utils
 } // namespace polydeal_hip

@@ -84,6 +84,22 @@ extern "C" int pdh_vmult(pdh_ctx *ctx, const double *x, double *y)
   return PDH_OK;
 }
 
+// r = b - A x: k_vmult into r, then one subtraction over the owned rows
+extern "C" int pdh_residual_device(pdh_ctx *ctx, const double *d_b, const double *d_x, double *d_r)
+{
+  PDH_TRY(need_problem(ctx, "pdh_residual_device"));
+  if (!d_b || !d_x || !d_r)
+    return fail(ctx, PDH_EINVAL, "b, x and r are required");
+  if (overlap(d_x, ctx->prob.n_rows_total, d_r, ctx->prob.n_rows_owned) || overlap(d_b, ctx->prob.n_rows_owned, d_r, ctx->prob.n_rows_owned))
+    return fail(ctx, PDH_EINVAL, "r overlaps x or b");
+  PDH_TRY(row_fits_lds(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  const PdhSolveArgs A = solve_args(ctx);
+  PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, d_r, nullptr, ctx->stream));
+  PDH_HIP(ctx, pdh_launch_residual_sub(ctx->prob.n_rows_owned, d_b, d_r, ctx->stream));
+  return PDH_OK;
+}
+
 extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
 {
   PDH_TRY(need_problem(ctx, "pdh_setup_preconditioner"));

@@ -1,4 +1,4 @@
-// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp), not installed: the context
+// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_transfer.cpp), not installed: the context
 // behind the opaque pdh_ctx of include/polydeal_hip.h, error reporting, the one device-buffer type, the alloc / upload helpers of
 // set-up and the entry guards.  No kernel header here: pdh_launch.h brings the kernels' argument structs and the launch records.
 #pragma once

@@ -4,6 +4,7 @@
 // pdhh_assemble_dg_matrix, which goes through the C ABI of polydeal_hip.h.
 #include "host/polydeal_host.h"
 
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -455,6 +456,61 @@ int pdhh_fill_injection_matrix(void *coarse, void *fine, int device, int64_t *ro
     std::memcpy(rowptr, rp.data(), rp.size() * sizeof(int64_t));
     std::memcpy(colind, ci.data(), ci.size() * sizeof(int32_t));
     std::memcpy(values, va.data(), va.size() * sizeof(double));
+    return 0;
+  });
+}
+
+// The parent map of two nested handlers (Utils::nested_parents): parent [n_fine_agglomerates].
+int pdhh_transfer_parents(void *coarse, void *fine, int32_t *parent)
+{
+  return guarded([&] {
+    const std::vector<int> p = Utils::nested_parents(static_cast<HandlerH *>(coarse)->ah, static_cast<HandlerH *>(fine)->ah, "pdhh_transfer_parents");
+    std::copy(p.begin(), p.end(), parent);
+    return 0;
+  });
+}
+// The pdh_transfer_desc of two nested handlers, independently owned; free it with pdhh_transfer_desc_destroy.
+void *pdhh_transfer_desc_create(void *coarse, void *fine)
+{
+  try
+    {
+      return new Utils::TransferDescription(static_cast<HandlerH *>(coarse)->ah, static_cast<HandlerH *>(fine)->ah);
+    }
+  catch (const std::exception &e)
+    {
+      g_host_err = e.what();
+      return nullptr;
+    }
+}
+const pdh_transfer_desc *pdhh_transfer_desc_c(void *th) { return &static_cast<Utils::TransferDescription *>(th)->c; }
+void pdhh_transfer_desc_destroy(void *th) { delete static_cast<Utils::TransferDescription *>(th); }
+// Utils::MGTransferAgglomeration through C on host vectors: which = 0 prolongate (dst [n_fine_dofs] overwritten), 1 prolongate_and_add,
+// 2 restrict_and_add (dst [n_coarse_dofs]).  One context and one transfer per call: the device path of the mirror end to end.
+int pdhh_mg_transfer_apply(void *coarse, void *fine, int device, int which, const double *src, int64_t n_src, double *dst, int64_t n_dst)
+{
+  return guarded([&] {
+    pdh_ctx *ctx = nullptr;
+    if (pdh_create(&ctx, device) != PDH_OK)
+      throw std::runtime_error(std::string("pdh_create: ") + pdh_last_error(nullptr));
+    struct Close
+    {
+      pdh_ctx *c;
+      ~Close() { pdh_destroy(c); }
+    } close{ctx};
+    const Utils::MGTransferAgglomeration T(static_cast<HandlerH *>(coarse)->ah, static_cast<HandlerH *>(fine)->ah, ctx);
+    const std::vector<double> s(src, src + n_src);
+    std::vector<double> d(dst, dst + n_dst);
+    if (which == 0)
+      T.prolongate(d, s);
+    else if (which == 1)
+      T.prolongate_and_add(d, s);
+    else if (which == 2)
+      T.restrict_and_add(d, s);
+    else
+      throw std::invalid_argument("which must be 0, 1 or 2");
+    if ((int64_t)d.size() != n_dst)
+      throw std::invalid_argument("dst has the wrong length");
+    std::copy(d.begin(), d.end(), dst);
     return 0;
   });
 }

@@ -15,6 +15,8 @@
 #include "pdh_solve.h"
 #include "pdh_terms_tables.h"
 
+struct PdhTransferArgs; // pdh_transfer.h
+
 // One resolved launch (host only).  kernel: host stub of the instantiation, NULL where nothing could be resolved (no such instantiation,
 // a grid beyond 2^31 - 1 blocks) - launching that answers hipErrorInvalidValue; grid 0: nothing to do, a successful no-op.
 struct PdhLaunch
@@ -141,4 +143,12 @@ hipError_t pdh_launch_cheb_update(const PdhSolveArgs *A, int first, int kind, co
 hipError_t pdh_launch_cg_direction(int64_t n_rows, int init, const double *z, double *p, const double *scal, hipStream_t stream);
 // one workgroup: partials -> scalars.  stage 0: rz, rr, bb;  1: pq, alpha;  2: rz, rr, beta
 hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, int stage, double *scal, hipStream_t stream);
+
+// pdh_transfer.hip (dim 2 | 3, n1d 2 .. 8; add: accumulate into the destination)
+// fine (+)= P coarse: one wave per max(1, 64 / n) fine polytopes
+hipError_t pdh_launch_prolongate(int dim, int n1d, int add, const PdhTransferArgs *A, const double *coarse, double *fine, hipStream_t stream);
+// coarse (+)= P^T fine: one wave per max(1, 64 / n) coarse polytopes, children in CSR order
+hipError_t pdh_launch_restrict(int dim, int n1d, int add, const PdhTransferArgs *A, const double *fine, double *coarse, hipStream_t stream);
+// r = b - r over n_rows entries (r holds A x)
+hipError_t pdh_launch_residual_sub(int64_t n_rows, const double *b, double *r, hipStream_t stream);
 }

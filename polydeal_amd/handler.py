@@ -81,6 +81,14 @@ def _lib():
                                                 C.c_int, C.c_int, C.c_void_p, C.c_int64]
         lib.pdhh_fill_injection_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int64]
+        lib.pdhh_transfer_parents.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pdhh_transfer_desc_create.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pdhh_transfer_desc_create.restype = C.c_void_p
+        lib.pdhh_transfer_desc_c.argtypes = [C.c_void_p]
+        lib.pdhh_transfer_desc_c.restype = C.POINTER(_capi.pdh_transfer_desc)
+        lib.pdhh_transfer_desc_destroy.argtypes = [C.c_void_p]
+        lib.pdhh_transfer_desc_destroy.restype = None
+        lib.pdhh_mg_transfer_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         _ready = True
     return lib
 
@@ -503,3 +511,48 @@ def fill_injection_matrix(coarse_ah: AgglomerationHandler, fine_ah: Agglomeratio
     if rc < 0:
         _raise()
     return rowptr, colind, values
+
+
+def transfer_parents(coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler):
+    """Coarse polytope of every fine one for two nested handlers (Utils::nested_parents; host only)."""
+    out = np.zeros(fine_ah.n_agglomerates, dtype=np.int32)
+    if _lib().pdhh_transfer_parents(coarse_ah.h, fine_ah.h, out.ctypes.data) < 0:
+        _raise()
+    return out
+
+
+def transfer_description(coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler):
+    """_capi.TransferDesc of two nested handlers (Utils::TransferDescription: boxes, dof offsets and parents of the host mirror)."""
+    lib = _lib()
+    th = lib.pdhh_transfer_desc_create(coarse_ah.h, fine_ah.h)
+    if not th:
+        _raise()
+    try:
+        c = lib.pdhh_transfer_desc_c(th).contents
+        dim = c.dim
+
+        def arr(addr, ctype, shape):
+            count = int(np.prod(shape))
+            return np.array((ctype * count).from_address(int(addr))).reshape(shape)
+        return _capi.TransferDesc(dim=dim, degree=c.degree, basis=c.basis,
+                                  fine_bbox=arr(c.fine_bbox, C.c_double, (c.n_fine, 2, dim)),
+                                  coarse_bbox=arr(c.coarse_bbox, C.c_double, (c.n_coarse, 2, dim)),
+                                  fine_dof_offset=arr(c.fine_dof_offset, C.c_int32, (c.n_fine,)),
+                                  coarse_dof_offset=arr(c.coarse_dof_offset, C.c_int32, (c.n_coarse,)),
+                                  parent=arr(c.parent, C.c_int32, (c.n_fine,)), n_fine_rows=c.n_fine_rows, n_coarse_rows=c.n_coarse_rows)
+    finally:
+        lib.pdhh_transfer_desc_destroy(th)
+
+
+def mg_transfer_apply(coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler, which, src, dst=None, device=0):
+    """Utils::MGTransferAgglomeration of the C++ mirror on host arrays: which = 'prolongate' | 'prolongate_and_add' |
+    'restrict_and_add' (the last two add to `dst`)."""
+    k = {"prolongate": 0, "prolongate_and_add": 1, "restrict_and_add": 2}[which]
+    s = np.ascontiguousarray(src, dtype=np.float64)
+    n_dst = coarse_ah.n_dofs if k == 2 else fine_ah.n_dofs
+    d = np.zeros(n_dst) if dst is None else np.array(dst, dtype=np.float64, copy=True)
+    if d.shape != (n_dst,):
+        raise ValueError("dst must have %d entries" % n_dst)
+    if _lib().pdhh_mg_transfer_apply(coarse_ah.h, fine_ah.h, device, k, s.ctypes.data, len(s), d.ctypes.data, len(d)) < 0:
+        _raise()
+    return d

@@ -55,3 +55,36 @@ def assemble_levels(levels, fe: FiniteElement, variant: SipVariant | None = None
     finally:
         ctx.close()
     return out
+
+
+def level_transfer(ctx, coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler):
+    """_capi.Transfer between two nested levels on the device of `ctx` (the reference's MGTransferAgglomeration, include/
+    multigrid_amg.h:439-490): description from the host mirror, 1-D factors built on the host, nothing but tables uploaded.  `ctx`
+    needs no resident problem; close the transfer before it."""
+    from ._capi import Transfer
+    from .handler import transfer_description
+
+    return Transfer(ctx, transfer_description(coarse_ah, fine_ah))
+
+
+def two_grid_cycle_device(fine_ctx, coarse_ctx, transfer, d_b, d_x, d_r, d_rc, d_ec, coarse_rel_tol=1e-13):
+    """One two-grid cycle on x composed of device calls alone; the caller owns every buffer (device pointers as ints: b, x, r of the
+    fine level's size, rc, ec of the coarse level's):
+      pre-smooth x (fine_ctx's Chebyshev smoother), r = b - A x, rc = P^T r, ec = 0, A_c ec = rc by coarse_ctx's CG to
+      coarse_rel_tol, x += P ec, post-smooth x.
+    Both contexts carry their assembled level matrix, the fine one with setup_chebyshev done, the coarse one with the preconditioner
+    of its CG; `transfer` lives on fine_ctx, whose stream orders the fine-level work.  Returns the info of the coarse solve."""
+    import ctypes as C
+
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    fine_ctx.chebyshev_step_device(d_b, d_x)
+    fine_ctx.residual_device(d_b, d_x, d_r)
+    transfer.restrict_device(d_r, d_rc)
+    fine_ctx.synchronize()  # the coarse context has a stream of its own
+    if hip.hipMemset(C.c_void_p(d_ec), 0, C.c_size_t(8 * transfer.desc.n_coarse_rows)) != 0 or hip.hipDeviceSynchronize() != 0:
+        raise RuntimeError("hipMemset of the coarse correction failed")
+    info = coarse_ctx.solve_cg_device(d_rc, d_ec, rel_tol=coarse_rel_tol)  # synchronises before it returns
+    transfer.prolongate_and_add_device(d_ec, d_x)
+    fine_ctx.chebyshev_step_device(d_b, d_x)
+    return info

@@ -12,6 +12,14 @@ that the two can be compared: k_cheb_update alone (a degree-1 application from a
 application (4 k_vmult + 5 updates, HIP events), the set-up with the inner build and the eigenvalue estimate apart, and full solves of
 b = A x* with block Jacobi and with Chebyshev of degree 2, 3 and 5: iterations, products with A and seconds.  The condition checked
 (field cheb5_within_bound): a degree-m application takes no longer than m x 1.10 block-Jacobi CG iterations measured here.
+
+Transfer section (--transfer, alone: nothing of the above runs; pdh_transfer_create), written to profiles/r08_transfer.json unless --out
+says otherwise: the headline level pair (64^3 cells, FE_DGQ(3), polytopes of 2^3 under polytopes of 4^3) and the FE_DGQ(2) pair of the same
+mesh, each level assembled in a context of its own.  prolongate, restrict and residual by HIP events, one two_grid_cycle_device
+(Chebyshev(3) over block Jacobi, block-Jacobi CG to 1e-13 on the coarse level) by wall time since it synchronises inside; the bytes
+each call must move (vectors + 1-D tables + index arrays; residual: the values + three vectors) and the resulting GB/s.  The one
+condition (field transfer_pair_under_cheb_update): prolongate + restrict together take less than one k_cheb_update on the fine level,
+measured in the same process.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -169,17 +177,99 @@ def full_solve(pa, torch, ctx, N, reps_unused=None):
             "residual": info["residual"], "rel_error_vs_x_star": err}
 
 
+def transfer_case(pa, torch, cells, p, reps):
+    """one level pair: fine polytopes of 2^3 cells under coarse ones of 4^3, each level resident in its own context"""
+    from polydeal_amd.handler import transfer_description
+    from polydeal_amd._capi import Transfer
+    from polydeal_amd.levels import two_grid_cycle_device
+
+    t0 = time.time()
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    fe = pa.FE_DGQ(3, p)
+    levels, ctxs = [], []
+    for block in (4, 2):
+        ah = pa.AgglomerationHandler(grid)
+        ah.define_block_agglomerates(block)
+        ah.initialize_fe_values(p + 1, p + 1)
+        ah.distribute_agglomerated_dofs(fe)
+        ctx = pa.Context(0)
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        ctx.set_problem(ah.flatten(pa.SipVariant.poisson_example(fe), False, False))
+        ctx.assemble_device()
+        levels.append(ah)
+        ctxs.append(ctx)
+    (coarse, fine), (ctx_c, ctx_f) = levels, ctxs
+    desc = transfer_description(coarse, fine)
+    tr = Transfer(ctx_f, desc)
+    Nf, Nc, n = fine.n_dofs, coarse.n_dofs, fe.n_dofs_per_cell
+    vec = lambda N: torch.rand(N, dtype=torch.float64, device="cuda")
+    xc, rf, xf, bf, yc = vec(Nc), vec(Nf), vec(Nf), vec(Nf), vec(Nc)
+    ctx_f.synchronize()
+    pro = event_times_ms(torch, lambda: tr.prolongate_device(xc.data_ptr(), xf.data_ptr()), reps)
+    res = event_times_ms(torch, lambda: tr.restrict_device(rf.data_ptr(), yc.data_ptr()), reps)
+    rsd = event_times_ms(torch, lambda: ctx_f.residual_device(bf.data_ptr(), xf.data_ptr(), rf.data_ptr()), reps)
+    est = ctx_f.setup_chebyshev("block_jacobi", degree=1)["estimate"]
+    upd = event_times_ms(torch, lambda: ctx_f.precondition_device(bf.data_ptr(), xf.data_ptr()), reps)  # one k_cheb_update
+    ctx_f.setup_chebyshev("block_jacobi", degree=3, max_eigenvalue=est)
+    ctx_c.setup_preconditioner("block_jacobi")
+    b, x, r = vec(Nf), torch.zeros(Nf, dtype=torch.float64, device="cuda"), torch.empty(Nf, dtype=torch.float64, device="cuda")
+    rc, ec = torch.empty(Nc, dtype=torch.float64, device="cuda"), torch.empty(Nc, dtype=torch.float64, device="cuda")
+    cyc, coarse_its = [], []
+    for _ in range(max(3, reps // 3) + 1):
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        info = two_grid_cycle_device(ctx_f, ctx_c, tr, b.data_ptr(), x.data_ptr(), r.data_ptr(), rc.data_ptr(), ec.data_ptr())
+        torch.cuda.synchronize()
+        cyc.append((time.perf_counter() - w0) * 1e3)
+        coarse_its.append(info["iterations"])
+    tab_bytes = 8.0 * desc.n_fine * 3 * (p + 1) ** 2
+    idx_bytes = 4.0 * (3 * desc.n_fine + 2 * desc.n_coarse + 1)  # parent, child_idx, fine_off; child_ptr, coarse_off
+    vec_bytes = 8.0 * (Nf + Nc)
+    moved = vec_bytes + tab_bytes + idx_bytes
+    res_bytes = 8.0 * (ctx_f.stats()["n_values"] + 3 * Nf)
+    upd_bytes = 8.0 * (desc.n_fine * n * n + 4 * Nf)  # the inverse blocks; b in, r, d, x out
+    rec = {
+        "element": "FE_DGQ(%d)" % p, "cells_per_axis": cells, "fine_polytopes": desc.n_fine, "coarse_polytopes": desc.n_coarse,
+        "fine_dofs": Nf, "coarse_dofs": Nc, "dofs_per_polytope": n,
+        "prolongate_ms_median": median(pro), "prolongate_ms_min": min(pro), "restrict_ms_median": median(res), "restrict_ms_min": min(res),
+        "transfer_bytes": moved, "transfer_table_bytes": tab_bytes,
+        "prolongate_GBps": moved / (median(pro) * 1e-3) / 1e9, "restrict_GBps": moved / (median(res) * 1e-3) / 1e9,
+        "residual_ms_median": median(rsd), "residual_bytes": res_bytes, "residual_GBps": res_bytes / (median(rsd) * 1e-3) / 1e9,
+        "cheb_update_ms_median": median(upd), "cheb_update_bytes": upd_bytes, "cheb_update_GBps": upd_bytes / (median(upd) * 1e-3) / 1e9,
+        "transfer_pair_ms": median(pro) + median(res),
+        "transfer_pair_under_cheb_update": bool(median(pro) + median(res) < median(upd)),
+        "two_grid_cycle_wall_ms_median": median(cyc[1:]), "two_grid_coarse_cg_iterations": coarse_its[1:],
+        "launches": len(pro), "case_wall_s": time.time() - t0,
+    }
+    tr.close()
+    ctx_f.close()
+    ctx_c.close()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-solve", action="store_true", help="skip the full headline solve")
     ap.add_argument("--chebyshev", action="store_true", help="add the Chebyshev section (FE_DGQ(3) diag_first and FE_AggloDGP(3))")
+    ap.add_argument("--transfer", action="store_true", help="the level-transfer section alone (default --out: profiles/r08_transfer.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.transfer:
+        out = {"tool": "tools/solve_bench.py --transfer", "version": pa.load_library().pdh_version().decode(),
+               "device": torch.cuda.get_device_name(0), "pairs": []}
+        for p in (3, 2):
+            out["pairs"].append(transfer_case(pa, torch, args.cells, p, args.reps))
+            print(json.dumps(out["pairs"][-1]), flush=True)
+        doc = json.dumps(out, indent=1)
+        with open(args.out or os.path.join(ROOT, "profiles", "r08_transfer.json"), "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     ctx = pa.Context(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
     out = {"tool": "tools/solve_bench.py", "version": pa.load_library().pdh_version().decode(),
