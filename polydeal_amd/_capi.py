@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PDH_LIB: another build of the library (diagnostic builds with experiment switches; tools/README.md)
+# PDH_LIB: another build of the library (the diagnostic builds of tools/README.md, another commit's build for an A/B)
 LIB_PATH = os.environ.get("PDH_LIB") or os.path.join(_HERE, "lib", "libpolydeal_hip.so")
 
 PDH_BASIS_DGQ = 0

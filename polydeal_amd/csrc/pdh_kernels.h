@@ -55,38 +55,20 @@
     }                                                                                                               \
   while (0)
 
-// Experiment switches for tools/ab_bench.py (never defined in the shipped build): time the kernels without their
-// epilogue (-DPDH_EXP_NOSTORE) or without their accumulation loops (-DPDH_EXP_NOCOMPUTE).  Measured on the
-// default bench workload: k_diag 5.75 ms compute-only / 0.42 ms store-only (5.9 together); k_offdiag 1.85 ms
-// compute-only / 1.90 ms store-only (2.47 together).
-#if defined(PDH_EXP_NOCOMPUTE)
-#define PDH_EXP_LOOPCOND &&(P.n < 0)
-#else
-#define PDH_EXP_LOOPCOND
-#endif
-#if defined(PDH_EXP_NOSTORE)
-#define PDH_EXP_EPILOGUE_GUARD                                                                     \
-  if (acc[0] != 1.2345e300)                                                                        \
-    return;
-#else
-#define PDH_EXP_EPILOGUE_GUARD
-#endif
+// Where the time of k_diag / k_offdiag goes, from builds without their epilogue or without their accumulation loops (default
+// bench workload, profiles/r01_probe_store_pattern.txt): k_diag 5.75 ms compute-only / 0.42 ms store-only (5.9 together);
+// k_offdiag 1.85 ms compute-only / 1.90 ms store-only (2.47 together).
 
 namespace pdh
 {
 // Workgroups are dealt round-robin over the 8 XCDs (observed, MI355X_MICROARCH.md: blocks b and b + 8 share one); each XCD has its own
 // L2.  Work item of block b such that every XCD works through ONE contiguous eighth of the n items: items that write neighbouring
 // pieces of the same rows (the blocks of a polytope's rows in the two-kernel forms) then meet in one L2, where partial lines merge
-// before they leave for HBM.  Speed only - correctness never depends on placement.  -DPDH_NO_XCD_CHUNKS: item = block.
+// before they leave for HBM.  Speed only - correctness never depends on placement (against item = block: profiles/r04_xcd_chunks.txt).
 __device__ __forceinline__ int xcd_chunked(int b, int n)
 {
-#ifdef PDH_NO_XCD_CHUNKS
-  (void)n;
-  return b;
-#else
   const int x = b & 7, k = b >> 3, q = n >> 3, r = n & 7;
   return x * q + (x < r ? x : r) + k;
-#endif
 }
 
 template <int I, int N, class F>
@@ -659,7 +641,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_diag(const PdhDev P, const int 
   // ---- volume term ---------------------------------------------------------------------------
   {
     const int64_t qb = P.vq_ptr[slot], qe = P.vq_ptr[slot + 1];
-    for (int64_t base = qb; base < qe PDH_EXP_LOOPCOND; base += CH)
+    for (int64_t base = qb; base < qe; base += CH)
       {
         const int cnt = (int)((qe - base < CH) ? (qe - base) : CH);
         __syncthreads();
@@ -722,7 +704,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_diag(const PdhDev P, const int 
   // ---- own-side face terms (all faces of the polytope, boundary included) ----------------------
   {
     const int64_t pb = P.ap_ptr[slot], pe = P.ap_ptr[slot + 1];
-    for (int64_t base = pb; base < pe PDH_EXP_LOOPCOND; base += CH)
+    for (int64_t base = pb; base < pe; base += CH)
       {
         const int cnt = (int)((pe - base < CH) ? (pe - base) : CH);
         __syncthreads();
@@ -779,7 +761,6 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_diag(const PdhDev P, const int 
   }
 
   // ---- epilogue: mirror + write rows in CSR order ------------------------------------------------
-  PDH_EXP_EPILOGUE_GUARD
   const int n = P.n;
   const int ncol_pad = 16 * NT + 2;
   double *strip = lds; // overlays the point records
@@ -849,7 +830,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_offdiag(const PdhDev P, const i
 
   const int kq = lane >> 4;
   const int64_t pb = P.it_pbeg[item], pe = pb + P.it_pcnt[item];
-  for (int64_t base = pb; base < pe PDH_EXP_LOOPCOND; base += CH)
+  for (int64_t base = pb; base < pe; base += CH)
     {
       const int cnt = (int)((pe - base < CH) ? (pe - base) : CH);
       __syncthreads();
@@ -902,7 +883,6 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_offdiag(const PdhDev P, const i
         }
     }
 
-  PDH_EXP_EPILOGUE_GUARD
   const int n = P.n;
   const int ncol_pad = 16 * NT + 2;
   double *strip = lds;

@@ -27,25 +27,6 @@
 #include "pdh_kernels.h"
 #include "pdh_moment_tables.h"
 
-// experiment switches (tools/ab_bench.py; never defined in the shipped build, results are garbage with them):
-// -DPDHM_EXP=1 no per-face tables, 2 no moment accumulation, 3 no contraction, 4 no stores
-#ifndef PDHM_EXP
-#define PDHM_EXP 0
-#endif
-#ifndef PDHM_OFF_FULL
-#define PDHM_OFF_FULL 0
-#endif
-#if PDHM_EXP == 4
-#define PDHM_STORE_OK (P.n < 0)
-#else
-#define PDHM_STORE_OK true
-#endif
-#if PDHM_EXP == 3
-#define PDHM_SLABS (P.n < 0 ? 4 : 0)
-#else
-#define PDHM_SLABS 4
-#endif
-
 namespace pdhm
 {
 using pdh::static_for;
@@ -910,11 +891,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
       pw = on ? P.vq_w[base + lane] : 0.0;
     };
     fetch(qb);
-#if PDHM_EXP == 2
-    for (int64_t base = qb; base < qe && P.n < 0; base += Acc::VCH)
-#else
     for (int64_t base = qb; base < qe; base += Acc::VCH)
-#endif
       {
         const int cnt = (int)((qe - base < Acc::VCH) ? (qe - base) : Acc::VCH);
         PDH_WAVE_SYNC();
@@ -927,17 +904,13 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
               w = pw;
             }
           fetch(base + Acc::VCH);
-#if PDHM_EXP != 5
           Acc::write_volume_record(work + lane * Acc::VREC, xu, w);
-#endif
         }
         PDH_WAVE_SYNC();
-#if PDHM_EXP != 6
         if (cnt == Acc::VCH)
           ma.volume_chunk_full();
         else
           ma.volume_chunk(work, cnt, lane);
-#endif
       }
   }
   // ---- moments of the own-side face points (all faces of the polytope, boundary included) ------------------
@@ -966,11 +939,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
     };
     if (pb < pe)
       fetch(pb);
-#if PDHM_EXP == 2
-    for (int64_t base = pb; base < pe && P.n < 0; base += Acc::CH)
-#else
     for (int64_t base = pb; base < pe; base += Acc::CH)
-#endif
       {
         const int cnt = (int)((pe - base < Acc::CH) ? (pe - base) : Acc::CH);
         PDH_WAVE_SYNC();
@@ -996,17 +965,13 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
             }
           if (base + Acc::CH < pe)
             fetch(base + Acc::CH);
-#if PDHM_EXP != 5
           Acc::write_face_record_half(work + pt * Acc::REC, half, xa, xb, s);
-#endif
         }
         PDH_WAVE_SYNC();
-#if PDHM_EXP != 6
         if (cnt == Acc::CH)
           ma.face_chunk_full();
         else
           ma.face_chunk(work, cnt, lane);
-#endif
       }
   }
   // gather: this lane's (a0,a1) row of every moment tensor
@@ -1047,7 +1012,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
         for (int k = 0; k < 16; ++k)
           T1B[k * 64 + lane] = 0.0;
 #pragma unroll 1
-        for (int k2 = 0; k2 < PDHM_SLABS; ++k2)
+        for (int k2 = 0; k2 < 4; ++k2)
           {
             PDH_WAVE_SYNC();
             if (act)
@@ -1114,8 +1079,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_mdiag(const PdhDev P, const dou
                 int pos = L + O;
                 if (P.diag_first)
                   pos = (O == R) ? 0 : (L + O + (O < R ? 1 : 0));
-                if (PDHM_STORE_OK)
-                  P.values[rbase + (int64_t)R * rlen + pos] = D3[cf][s0];
+                P.values[rbase + (int64_t)R * rlen + pos] = D3[cf][s0];
               });
             });
           }
@@ -1262,11 +1226,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
   double *tabEQ = lds;                // [3][PAIRS][RS]
   double *tabHQ = lds + 3 * M::LTAB;  // [3][PAIRS][RS]
   double *work = lds + 6 * M::LTAB;
-#if PDHM_EXP == 1
-  if (lane < DIM * N1D * N1D && P.n < 0)
-#else
   if (lane < DIM * N1D * N1D)
-#endif
     {
       const int c = lane / (N1D * N1D), k = (lane / N1D) % N1D, l = lane % N1D;
       // this lane's direction: selected with exact 0/1 factors (an if-chain over the arrays is turned into an indexed
@@ -1344,11 +1304,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
     };
     if (pb < pe)
       fetch(pb);
-#if PDHM_EXP == 2
-    for (int64_t base = pb; base < pe && P.n < 0; base += Acc::CH)
-#else
     for (int64_t base = pb; base < pe; base += Acc::CH)
-#endif
       {
         const int cnt = (int)((pe - base < Acc::CH) ? (pe - base) : Acc::CH);
         PDH_WAVE_SYNC();
@@ -1376,12 +1332,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
           Acc::write_face_record_half(work + pt * Acc::REC, half, xa, xb, s);
         }
         PDH_WAVE_SYNC();
-#if PDHM_OFF_FULL
-        if (cnt == Acc::CH)
-          ma.face_chunk_full();
-        else
-#endif
-          ma.face_chunk(work, cnt, lane);
+        ma.face_chunk(work, cnt, lane);
       }
   }
   double accS[NAP], accN[DIM][NAP];
@@ -1424,7 +1375,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
         T1Off t1o;
         t1o.init(a0, a1);
 #pragma unroll 1
-        for (int s2 = 0; s2 < PDHM_SLABS; ++s2)
+        for (int s2 = 0; s2 < 4; ++s2)
           {
             PDH_WAVE_SYNC();
             if (act)
@@ -1471,8 +1422,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
                 static_for<0, 4>([&](auto s0_) {
                   constexpr int s0 = s0_;
                   const int R = s0 + 4 * cf + 16 * s2;
-                  if (PDHM_STORE_OK)
-                    P.values[qbase + (int64_t)R * qlen + post + O] = D3[cf][s0];
+                  P.values[qbase + (int64_t)R * qlen + post + O] = D3[cf][s0];
                 });
               });
             // A[P,Q]: columns 16 s2 .. 16 s2 + 15 of every row O, through an LDS staging tile (full 128-byte lines)
@@ -1492,8 +1442,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
               for (int jb = 0; jb < 64; jb += 4)
                 {
                   const int j = jb + (lane >> 4);
-                  if (PDHM_STORE_OK)
-                    P.values[rbase + (int64_t)j * rlen + pos0 + 16 * s2 + cc] = stage[j * SR + cc];
+                  P.values[rbase + (int64_t)j * rlen + pos0 + 16 * s2 + cc] = stage[j * SR + cc];
                 }
             }
           }
@@ -1526,9 +1475,6 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
   const int post = P.it_pos_t[item];
   constexpr int SROW = N1D * N1D + 1; // staging row stride (odd: conflict-free)
   int col_begin = 0;
-#if PDHM_EXP == 3
-  if (P.n < 0)
-#endif
 #pragma unroll 1
   for (int s2 = 0; s2 < N1D && col_begin < n; ++s2)
     {
@@ -1582,7 +1528,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
       static_for<0, N1D * N1D>([&](auto r_) {
         constexpr int r = r_;
         cols_of[r] = row_of(live, packed_own, r % N1D, r / N1D, s2);
-        if (qslot >= 0 && cols_of[r] >= 0 && live && PDHM_STORE_OK)
+        if (qslot >= 0 && cols_of[r] >= 0 && live)
           P.values[qbase + (int64_t)cols_of[r] * qlen + post + lane] = out[r];
       });
       // A[P,Q]: this slab holds columns [col_begin,col_end) of every row i.  Through an LDS staging tile so that one
@@ -1603,7 +1549,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_moffdiag(const PdhDev P, const 
         for (int ib = 0; ib < n; ib += PDH_WAVE / W)
           {
             const int i = ib + lane / W;
-            if (i < n && cc < cols && lane < (PDH_WAVE / W) * W && PDHM_STORE_OK)
+            if (i < n && cc < cols && lane < (PDH_WAVE / W) * W)
               P.values[rbase + (int64_t)i * rlen + pos0 + col_begin + cc] = stage[i * SROW + cc];
           }
       }

@@ -50,28 +50,13 @@
 // tests otherwise (a store directly behind an MFMA result; a row pointer restored from a spilled SGPR by v_readlane right in
 // front of the store: "VALU writes SGPR -> VMEM reads it" needs five wait states, the store went to a stale address).  The
 // resource's size is the polytope's n rows: an offset that is off is DROPPED by the bounds check instead of written.
-// Carries travel through LDS and are read back by lane 0 alone (PDHR_CARRY_READ8 below, plain C++ in the shipped build): no asm
+// Carries travel through LDS and are read back by lane 0 alone (carry_read8 below, plain C++): no asm
 // statement of this file issues a memory instruction the compiler cannot see or changes EXEC (tools/isa_lint.py checks the
 // generated code object for both).
 #pragma once
 #include "pdh_moment.h"
 
 #include "pdh_rows_tables.h"
-
-// experiment switches (tools/ab_bench.py; never defined in the shipped build): -DPDHR_EXP=1 no coupling blocks (P5),
-// 2 no diagonal block (P4), 3 no faces (P2), 4 no volume (P1), 5 P5 without its global stores, 6 no row stores at all
-#ifndef PDHR_EXP
-#define PDHR_EXP 0
-#endif
-// 1: the blocks RIGHT of the diagonal (aligned pieces, no carries) are written before the diagonal block, the blocks left of it
-// after: the row stores of a polytope come in three bursts (192 | 64 | 192 for a block-shaped polytope) instead of one of
-// 448 at the end - the kernel is bound by how well its stores overlap with the arithmetic of the other waves of the CU
-#ifndef PDHR_SPLIT
-#define PDHR_SPLIT 1
-#endif
-#ifndef PDHR_STORE_AUX
-#define PDHR_STORE_AUX 18 // gfx940+ cache-policy bits of the row stores: 1 = sc0, 2 = nt, 16 = sc1
-#endif
 
 // -DPDHR_CHECK (diagnostic builds only): every data-dependent point index of a global load is checked against the size of
 // its array; a violation is recorded in the stamp buffer (slot 15: code | index << 8, slot 14: the wave's slot) and the index is
@@ -112,74 +97,28 @@ __device__ __forceinline__ int64_t pdhr_checked(int64_t idx, int64_t n, int code
 #define PDHR_ACC(var)
 #endif
 
-// Eight carries of a shifted piece, read from LDS by lane 0 ALONE straight into the registers that hold the products of rows
-// 8 g .. 8 g + 7 (the other lanes keep theirs): the statement narrows EXEC to lane 0 around eight ds_read_b64 and waits for them
-// itself, so nothing is outstanding that the compiler does not know of.  It SAVES the mask it finds and restores exactly that
-// (round 3 restored the constant -1, i.e. relied on the compiler never placing the statement under a partial mask - true of the
-// code it generated, checked by tools/isa_lint.py rule B, but not something an asm string may assume).  -DPDHR_EXEC_CONST
-// (diagnostic builds only) brings the old form back.
-#if !defined(PDHR_CARRY_ASM) && !defined(PDHR_EXEC_CONST)
-// Default since round 4: plain C++ - `if (lane == 0)` around eight LDS reads.  hipcc turns it into s_and_saveexec / ds_read2_b64 x 4
-// / s_or exec, i.e. the same instructions as the hand-written statement below (fewer: the reads pair up), counts the reads in its
-// own s_waitcnt bookkeeping and owns EXEC; no asm statement of the library changes EXEC any more.  -DPDHR_CARRY_ASM brings the
-// asm form back (A/B, tools/ab_bench.py).
-#define PDHR_CARRY_READ8(V0, V1, V2, V3, V4, V5, V6, V7, CADDR, G)                                                    \
-  do                                                                                                                  \
-    {                                                                                                                 \
-      if (lane == 0)                                                                                                  \
-        {                                                                                                             \
-          const double *cp_ = csrc + 8 * (G);                                                                         \
-          V0 = cp_[0], V1 = cp_[1], V2 = cp_[2], V3 = cp_[3], V4 = cp_[4], V5 = cp_[5], V6 = cp_[6], V7 = cp_[7];     \
-        }                                                                                                             \
-      (void)(CADDR);                                                                                                  \
-    }                                                                                                                 \
-  while (0)
-#elif defined(PDHR_EXEC_CONST)
-#define PDHR_CARRY_READ8(V0, V1, V2, V3, V4, V5, V6, V7, CADDR, G)                                                    \
-  asm volatile("s_mov_b64 exec, 1\n\t"                                                                               \
-               "ds_read_b64 %0, %8 offset:%9\n\t"                                                                    \
-               "ds_read_b64 %1, %8 offset:%10\n\t"                                                                   \
-               "ds_read_b64 %2, %8 offset:%11\n\t"                                                                   \
-               "ds_read_b64 %3, %8 offset:%12\n\t"                                                                   \
-               "ds_read_b64 %4, %8 offset:%13\n\t"                                                                   \
-               "ds_read_b64 %5, %8 offset:%14\n\t"                                                                   \
-               "ds_read_b64 %6, %8 offset:%15\n\t"                                                                   \
-               "ds_read_b64 %7, %8 offset:%16\n\t"                                                                   \
-               "s_mov_b64 exec, -1\n\t"                                                                              \
-               "s_waitcnt lgkmcnt(0)"                                                                                \
-               : "+v"(V0), "+v"(V1), "+v"(V2), "+v"(V3), "+v"(V4), "+v"(V5), "+v"(V6), "+v"(V7)                      \
-               : "v"(CADDR), "n"(64 * (G) + 0), "n"(64 * (G) + 8), "n"(64 * (G) + 16), "n"(64 * (G) + 24),           \
-                 "n"(64 * (G) + 32), "n"(64 * (G) + 40), "n"(64 * (G) + 48), "n"(64 * (G) + 56))
-#else
-#define PDHR_CARRY_READ8(V0, V1, V2, V3, V4, V5, V6, V7, CADDR, G)                                                    \
-  do                                                                                                                  \
-    {                                                                                                                 \
-      unsigned long long exec_saved_;                                                                                 \
-      asm volatile("s_mov_b64 %8, exec\n\t"                                                                          \
-                   "s_mov_b64 exec, 1\n\t"                                                                           \
-                   "ds_read_b64 %0, %9 offset:%10\n\t"                                                               \
-                   "ds_read_b64 %1, %9 offset:%11\n\t"                                                               \
-                   "ds_read_b64 %2, %9 offset:%12\n\t"                                                               \
-                   "ds_read_b64 %3, %9 offset:%13\n\t"                                                               \
-                   "ds_read_b64 %4, %9 offset:%14\n\t"                                                               \
-                   "ds_read_b64 %5, %9 offset:%15\n\t"                                                               \
-                   "ds_read_b64 %6, %9 offset:%16\n\t"                                                               \
-                   "ds_read_b64 %7, %9 offset:%17\n\t"                                                               \
-                   "s_mov_b64 exec, %8\n\t"                                                                          \
-                   "s_waitcnt lgkmcnt(0)"                                                                            \
-                   : "+v"(V0), "+v"(V1), "+v"(V2), "+v"(V3), "+v"(V4), "+v"(V5), "+v"(V6), "+v"(V7), "=&s"(exec_saved_) \
-                   : "v"(CADDR), "n"(64 * (G) + 0), "n"(64 * (G) + 8), "n"(64 * (G) + 16), "n"(64 * (G) + 24),       \
-                     "n"(64 * (G) + 32), "n"(64 * (G) + 40), "n"(64 * (G) + 48), "n"(64 * (G) + 56));                \
-      (void)exec_saved_;                                                                                              \
-    }                                                                                                                 \
-  while (0)
-#endif
-
 namespace pdhr
 {
 using pdh::static_for;
 using pdhm::d2_t;
 typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
+
+// gfx940+ cache-policy bits of the row stores of FE_DGQ(3): 1 = sc0, 2 = nt, 16 = sc1 (why sc1 | nt: at row_store in k_rows; how the
+// policies compare between contexts: profiles/r03_placement_spread.txt)
+constexpr int ROW_STORE_AUX = 18;
+
+// Eight carries of a shifted piece, read from LDS by lane 0 ALONE straight into the registers v[0 .. 7] that hold the products of
+// eight rows (the other lanes keep theirs).  Plain C++: hipcc turns it into s_and_saveexec / ds_read2_b64 x 4 / s_or exec, counts the
+// reads in its own s_waitcnt bookkeeping and owns EXEC - no asm statement of the library changes EXEC (tests/test_isa_lint.py; the
+// asm forms this replaced: DESIGN.md 4c).
+__device__ __forceinline__ void carry_read8(double *v, const double *carries, int lane)
+{
+  if (lane == 0)
+    {
+      v[0] = carries[0], v[1] = carries[1], v[2] = carries[2], v[3] = carries[3];
+      v[4] = carries[4], v[5] = carries[5], v[6] = carries[6], v[7] = carries[7];
+    }
+}
 
 constexpr int FREC = 33; // face record: L_i[8], (s_t L_j)[3][8], pad (odd stride)
 constexpr int FCH = 32;  // face points per chunk
@@ -425,15 +364,12 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
   // the polytope's rows as a buffer: n rows of rlen values from rbase on (see "Row stores" at the top of this file)
   const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(P.values + rbase, 0, NF * rlen * 8, 0x00020000);
   auto row_store = [&](double v, uint32_t lane_bytes, uint32_t row_bytes) {
-#if PDHR_EXP == 6
-    if (P.n < 0) // (experiment: everything computed, nothing stored)
-#endif
     // cache policy sc1 | nt: the values are written once and not read again by this kernel; written through (the line is not kept in
     // the XCD's L2) the same stores run 5 % faster in the store-only twin of this kernel (tools/probes/rows_store_probe.hip:
     // 1.37 -> 1.30 ms at 8 waves per CU)
     // (the streamed kinds keep the default policy: their rows are not multiples of 128 bytes, neighbouring pieces share lines, and
     // written through the halves of a shared line no longer merge in L2 - FE_DGQ(2) 0.74 -> 0.79 ms with sc1)
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, SMALL ? 0 : PDHR_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, SMALL ? 0 : ROW_STORE_AUX);
   };
   // the face table of the polytope lives in the lanes (lane t = face t); a face's entries are read with v_readlane
   const long long pb_ = __double_as_longlong(cur.e[0]);
@@ -472,11 +408,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
       const int m3 = tn * tn * tn;
       const int ncell = (int)((qe - qb) / m3);
       double *mv = W; // [16 cells][3][8]
-#if PDHR_EXP == 4
-      for (int c0 = 0; c0 < ncell && P.n < 0; c0 += 16)
-#else
       for (int c0 = 0; c0 < ncell; c0 += 16)
-#endif
         {
           const int nb = ncell - c0 < 16 ? ncell - c0 : 16;
           PDH_WAVE_SYNC();
@@ -558,11 +490,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
       ma.volume_chunk_full(); // dead points carry zero weights
       PDH_WAVE_SYNC();
     };
-#if PDHR_EXP == 4
-    for (int64_t base = qb; base < qe && P.n < 0; base += 2 * Acc::VCH)
-#else
     for (int64_t base = qb; base < qe; base += 2 * Acc::VCH)
-#endif
       {
         vchunk(va, base);
         if (base + Acc::VCH < qe)
@@ -723,11 +651,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
 #ifdef PDHR_STAMP
         long long tt_task = 0, tt_face = 0;
 #endif
-#if PDHR_EXP == 3
-        while (tb < nfaces && P.n < 0)
-#else
         while (tb < nfaces)
-#endif
           {
             int te = tb, ntask = 0;
             while (te < nfaces)
@@ -977,11 +901,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
 #endif
       }
     else if constexpr (GENERAL)
-#if PDHR_EXP == 3
-    if (nfaces > 0 && P.n < 0)
-#else
     if (nfaces > 0)
-#endif
       {
         // Chunk cursors: (face, pass, first point).  The point data of a chunk is requested DEPTH chunks ahead of its use
         // into a ring of register sets - a global load takes ~7k cycles under the store traffic of this kernel (in-kernel
@@ -1503,21 +1423,19 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
 
   // ================= coupling blocks (FE_DGQ(3), one plane per neighbour): P5 of the phase list ===========================
   // LEFT_PASS = false: the blocks right of the diagonal (every block in the ascending layout) - plain aligned pieces, no
-  // dependence on anything but their own face: written HERE, before the diagonal block (PDHR_SPLIT).  LEFT_PASS = true: the
+  // dependence on anything but their own face: written HERE, before the diagonal block.  LEFT_PASS = true: the
   // blocks left of the diagonal, whose pieces start with the last column of the block before (the first one with the
-  // diagonal entry, which P4 leaves in diagv): after P4.
+  // diagonal entry, which P4 leaves in diagv): after P4.  The row stores of a polytope so come in three bursts (192 | 64 | 192 for a
+  // block-shaped polytope) instead of one of 448 at the end - the kernel is bound by how well its stores overlap with the
+  // arithmetic of the other waves of the CU.
   auto coupling_blocks = [&](auto left_pass_) {
     constexpr bool LEFT_PASS = left_pass_;
     // (the ascending layout has aligned pieces only: one pass, after the diagonal block - before it the moment accumulators
     // are still live and the pass would spill)
-    constexpr bool SPLIT = PDHR_SPLIT && SHIFTED;
+    constexpr bool SPLIT = SHIFTED;
     double carry = 0.0; // lane R: the value that lane 0 stores in row R of the next piece
     bool first_left = true;
-#if PDHR_EXP == 1
-    for (int t = n_bdry; t < nfaces && P.n < 0; ++t)
-#else
     for (int t = n_bdry; t < nfaces; ++t)
-#endif
       {
         const int b = rl_i(t_blk, t);
         const int c = rl_i(t_axis, t);
@@ -1548,8 +1466,6 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
         if (left && !first_piece)
           ctab[lane] = carry;
         const double *csrc = first_piece ? diagv : ctab; // uniform
-        typedef __attribute__((address_space(3))) const char lds_cchar;
-        const unsigned caddr = (unsigned)(uintptr_t)(lds_cchar *)reinterpret_cast<const char *>(csrc);
         if (left)
           PDH_WAVE_SYNC();
         const uint32_t rowp = 64u * 8u * (uint32_t)b; // uniform: byte offset of the piece in row 0
@@ -1570,18 +1486,15 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
               v[r_] = Cl[kc] * sc[u];
             });
             if constexpr (LEFT)
-              PDHR_CARRY_READ8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], caddr, g); // (one self-contained statement)
+              carry_read8(v, csrc + 8 * g, lane);
             static_for<0, 8>([&](auto r_) {
-#if PDHR_EXP == 5
-              if (P.n < 0)
-#endif
-                row_store(v[r_], loff, rowrun); // (a running offset: 64 precomputed row offsets would be spilled scalars)
+              row_store(v[r_], loff, rowrun); // (a running offset: 64 precomputed row offsets would be spilled scalars)
               rowrun += (uint32_t)rlen * 8u;
             });
           });
         };
         using std::integral_constant;
-        // (with PDHR_SPLIT a pass meets one kind of piece only: the other kind's code is not instantiated for it)
+        // (with SPLIT a pass meets one kind of piece only: the other kind's code is not instantiated for it)
         if (left)
           {
             if constexpr (LEFT_PASS || !SPLIT)
@@ -1610,7 +1523,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
         carry = next_carry;
       }
   };
-  if constexpr (!SMALL && !MULTI && PDHR_SPLIT && SHIFTED)
+  if constexpr (!SMALL && !MULTI && SHIFTED)
     coupling_blocks(std::false_type{});
 
   m2_ahead_fl = -1; // (MULTI: a value requested ahead by P3 is not carried through the diagonal block)
@@ -1684,11 +1597,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
       long long tp1 = 0, tp2 = 0, tp3 = 0;
 #endif
 #pragma unroll 1
-#if PDHR_EXP == 2
-      for (int k2 = 0; k2 < N1D && P.n < 0; ++k2)
-#else
       for (int k2 = 0; k2 < N1D; ++k2)
-#endif
         {
           PDH_WAVE_SYNC();
           PDHR_T0();
@@ -1811,11 +1720,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
     long long tq1 = 0, tq2 = 0, tq3 = 0;
 #endif
 #pragma unroll 1
-#if PDHR_EXP == 2
-    for (int k2 = 0; k2 < 4 && P.n < 0; ++k2)
-#else
     for (int k2 = 0; k2 < 4; ++k2)
-#endif
       {
         PDH_WAVE_SYNC();
 #ifdef PDHR_STAMP
@@ -2019,11 +1924,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
       (void)total, (void)mis, (void)e, (void)nit;
       const uint32_t loff5 = (uint32_t)lane * 8u;
 #pragma unroll 2
-#if PDHR_EXP == 1
-      for (int R = 0; R < NF && P.n < 0; ++R)
-#else
       for (int R = 0; R < NF; ++R)
-#endif
         {
           static_for<0, MAXPC>([&](auto pc_) {
             constexpr int pc = pc_;
@@ -2044,11 +1945,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
                       const double dd = Dblk[R * NF + R];
                       val = lane == 0 ? dd : val;
                     }
-#if PDHR_EXP == 5
-                if (valid[pc] && P.n < 0)
-#else
                 if (valid[pc])
-#endif
                   {
                     row_store(val, loff5, (uint32_t)(R * rlen + pc * 64) * 8u); // scalar row / piece offset + lane offset
                   }
@@ -2065,11 +1962,7 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
 #ifdef PDHR_STAMP
     long long tb_S = 0, tb_out = 0;
 #endif
-#if PDHR_EXP == 1
-    while (t < nfaces && P.n < 0)
-#else
     while (t < nfaces)
-#endif
       {
         const int b = rl_i(t_blk, t);
         int te = t + 1;
@@ -2090,151 +1983,88 @@ __global__ void __launch_bounds__(PDH_WAVE, 2) k_rows(const PdhDev P, const PdhR
         if (left && !first_piece)
           ctab[lane] = carry;
         const double *csrc = first_piece ? diagv : ctab; // uniform
+        // (caddr is read by nothing; without it and its mention beside carry_read8 below, hipcc generates other code for
+        // k_rows<4, 0, false, true, true> - tools/device_code_diff.py)
         typedef __attribute__((address_space(3))) const char lds_cchar;
         const unsigned caddr = (unsigned)(uintptr_t)(lds_cchar *)reinterpret_cast<const char *>(csrc);
         double next_carry = 0.0;
         using std::integral_constant;
-#ifdef PDHR_MULTI_FUSED
-        // (diagnostic build only, never shipped: round 3's first MULTI version, which multiplied and stored the rows of a
-        // single-plane neighbour directly - the block kernel's fused path - next to the accumulating path, and faulted on the
-        // device.  Kept so that tools/isa_lint.py can be run on exactly that code: DESIGN.md 4c, "the fused-path fault".)
-        if (te - t == 1)
-          {
-            PDH_WAVE_SYNC();
-            build_S(t);
-            const int c = rl_i(t_axis, t);
-            const int lc = digit_c(jcol, c), vt = digits_t(jcol, c);
-            double Cl[4], sc[16];
-            for (int k = 0; k < 4; ++k)
-              Cl[k] = Cbuf[k * 4 + lc];
-            for (int u = 0; u < 16; ++u)
-              sc[u] = Sbuf[u * 16 + vt];
-            next_carry = left ? last_column(c) : 0.0;
-            if (left)
-              PDH_WAVE_SYNC();
-            auto rows = [&, lane_off](auto c_, auto left_) {
-              constexpr int cc = c_;
-              constexpr bool LEFT = left_;
-              const uint32_t loff = lane_off;
-              uint32_t rowrun = rowp;
-              static_for<0, 8>([&](auto g_) {
-                constexpr int g = g_;
-                double v[8];
-                static_for<0, 8>([&](auto r_) {
-                  constexpr int R = 8 * g + r_;
+        // acc[r] = sum_e C_e[k_c(R), l_c(j)] S_e[u(R), v(j)], in two halves of 32 rows (64 accumulators do not fit the
+        // register file next to what lives across this phase).  S_e / C_e of the first three planes of a neighbour stay in
+        // LDS side by side (W + 704 ..., behind the scratch of build_S) for the second half; further planes are rebuilt.
+        // (A variant that multiplied and stored the rows of single-plane neighbours directly, like the block-shaped
+        // kernel does, faulted on the device in all its four instantiations - stores through a corrupted base - while this
+        // form is correct; the cause was not found in the generated code, see profiles/README.md, r03.)
+        uint32_t rowrun = rowp;
+        static_for<0, 2>([&](auto half_) {
+          constexpr int half = half_;
+          double acc[32];
+          static_for<0, 32>([&](auto r_) { acc[r_] = 0.0; });
+          for (int e = t; e < te; ++e)
+            {
+              const int kslot = e - t;
+              Sdst = kslot < 3 ? W + 704 + 272 * kslot : Sbuf;
+              Cdst = kslot < 3 ? W + 704 + 272 * kslot + 256 : Cbuf;
+              if (half == 0 || kslot >= 3)
+                {
+                  PDHR_T0();
+                  PDH_WAVE_SYNC();
+                  build_S(e);
+                  PDHR_ACC(tb_S);
+                }
+              const int c = rl_i(t_axis, e);
+              const int lc = digit_c(jcol, c), vt = digits_t(jcol, c);
+              double Cl[4], sc[16];
+              for (int k = 0; k < 4; ++k)
+                Cl[k] = Cdst[k * 4 + lc];
+              for (int u = 0; u < 16; ++u)
+                sc[u] = Sdst[u * 16 + vt];
+              if (half == 0 && left)
+                next_carry += last_column(c);
+              auto add = [&](auto c_) {
+                constexpr int cc = c_;
+                static_for<0, 32>([&](auto r_) {
+                  constexpr int R = 32 * half + r_;
                   constexpr int kc = (R >> (2 * cc)) & 3;
                   constexpr int k0 = R & 3, k1 = (R >> 2) & 3, k2 = (R >> 4) & 3;
                   constexpr int u = cc == 0 ? (k1 + 4 * k2) : (cc == 1 ? (k0 + 4 * k2) : (k0 + 4 * k1));
-                  v[r_] = Cl[kc] * sc[u];
+                  acc[r_] += Cl[kc] * sc[u];
                 });
-                if constexpr (LEFT)
-                  PDHR_CARRY_READ8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], caddr, g);
-                static_for<0, 8>([&](auto r_) {
-                  row_store(v[r_], loff, rowrun);
-                  rowrun += (uint32_t)rlen * 8u;
-                });
-              });
-            };
-            if (left)
-              {
-                if (c == 0)
-                  rows(integral_constant<int, 0>{}, std::true_type{});
-                else if (c == 1)
-                  rows(integral_constant<int, 1>{}, std::true_type{});
-                else
-                  rows(integral_constant<int, 2>{}, std::true_type{});
-              }
-            else
-              {
-                if (c == 0)
-                  rows(integral_constant<int, 0>{}, std::false_type{});
-                else if (c == 1)
-                  rows(integral_constant<int, 1>{}, std::false_type{});
-                else
-                  rows(integral_constant<int, 2>{}, std::false_type{});
-              }
-          }
-        else
-#endif
-        {
-          // acc[r] = sum_e C_e[k_c(R), l_c(j)] S_e[u(R), v(j)], in two halves of 32 rows (64 accumulators do not fit the
-          // register file next to what lives across this phase).  S_e / C_e of the first three planes of a neighbour stay in
-          // LDS side by side (W + 704 ..., behind the scratch of build_S) for the second half; further planes are rebuilt.
-          // (A variant that multiplied and stored the rows of single-plane neighbours directly, like the block-shaped
-          // kernel does, faulted on the device in all its four instantiations - stores through a corrupted base - while this
-          // form is correct; the cause was not found in the generated code, see profiles/README.md, r03.)
-          uint32_t rowrun = rowp;
-          static_for<0, 2>([&](auto half_) {
-            constexpr int half = half_;
-            double acc[32];
-            static_for<0, 32>([&](auto r_) { acc[r_] = 0.0; });
-            for (int e = t; e < te; ++e)
-              {
-                const int kslot = e - t;
-                Sdst = kslot < 3 ? W + 704 + 272 * kslot : Sbuf;
-                Cdst = kslot < 3 ? W + 704 + 272 * kslot + 256 : Cbuf;
-                if (half == 0 || kslot >= 3)
-                  {
-                    PDHR_T0();
-                    PDH_WAVE_SYNC();
-                    build_S(e);
-                    PDHR_ACC(tb_S);
-                  }
-                const int c = rl_i(t_axis, e);
-                const int lc = digit_c(jcol, c), vt = digits_t(jcol, c);
-                double Cl[4], sc[16];
-                for (int k = 0; k < 4; ++k)
-                  Cl[k] = Cdst[k * 4 + lc];
-                for (int u = 0; u < 16; ++u)
-                  sc[u] = Sdst[u * 16 + vt];
-                if (half == 0 && left)
-                  next_carry += last_column(c);
-                auto add = [&](auto c_) {
-                  constexpr int cc = c_;
-                  static_for<0, 32>([&](auto r_) {
-                    constexpr int R = 32 * half + r_;
-                    constexpr int kc = (R >> (2 * cc)) & 3;
-                    constexpr int k0 = R & 3, k1 = (R >> 2) & 3, k2 = (R >> 4) & 3;
-                    constexpr int u = cc == 0 ? (k1 + 4 * k2) : (cc == 1 ? (k0 + 4 * k2) : (k0 + 4 * k1));
-                    acc[r_] += Cl[kc] * sc[u];
-                  });
-                };
-                if (c == 0)
-                  add(integral_constant<int, 0>{});
-                else if (c == 1)
-                  add(integral_constant<int, 1>{});
-                else
-                  add(integral_constant<int, 2>{});
-              }
-            if (half == 0 && left)
-              PDH_WAVE_SYNC(); // (ctab written above is read below)
-            auto out = [&](auto left_) {
-              constexpr bool LEFT = left_;
-              static_for<0, 4>([&](auto g_) {
-                constexpr int g = 4 * half + g_;
-                if constexpr (LEFT)
-                  PDHR_CARRY_READ8(acc[8 * g_ + 0], acc[8 * g_ + 1], acc[8 * g_ + 2], acc[8 * g_ + 3], acc[8 * g_ + 4], acc[8 * g_ + 5],
-                                   acc[8 * g_ + 6], acc[8 * g_ + 7], caddr, g);
-                static_for<0, 8>([&](auto r_) {
-#if PDHR_EXP == 5
-                  if (P.n < 0)
-#endif
-                    row_store(acc[8 * g_ + r_], lane_off, rowrun);
-                  rowrun += (uint32_t)rlen * 8u;
-                });
-              });
-            };
-            {
-              PDHR_T0();
-              if (left)
-                out(std::true_type{});
+              };
+              if (c == 0)
+                add(integral_constant<int, 0>{});
+              else if (c == 1)
+                add(integral_constant<int, 1>{});
               else
-                out(std::false_type{});
-              PDHR_ACC(tb_out);
+                add(integral_constant<int, 2>{});
             }
-          });
-          Sdst = Sbuf, Cdst = Cbuf;
-        }
+          if (half == 0 && left)
+            PDH_WAVE_SYNC(); // (ctab written above is read below)
+          auto out = [&](auto left_) {
+            constexpr bool LEFT = left_;
+            static_for<0, 4>([&](auto g_) {
+              constexpr int g = 4 * half + g_;
+              if constexpr (LEFT)
+                {
+                  carry_read8(acc + 8 * g_, csrc + 8 * g, lane);
+                  (void)caddr;
+                }
+              static_for<0, 8>([&](auto r_) {
+                row_store(acc[8 * g_ + r_], lane_off, rowrun);
+                rowrun += (uint32_t)rlen * 8u;
+              });
+            });
+          };
+          {
+            PDHR_T0();
+            if (left)
+              out(std::true_type{});
+            else
+              out(std::false_type{});
+            PDHR_ACC(tb_out);
+          }
+        });
+        Sdst = Sbuf, Cdst = Cbuf;
         PDH_WAVE_SYNC();
         carry = next_carry;
         t = te;

@@ -15,20 +15,16 @@
 //      l - 1 (its own table offsets), lane 0 the last column of the block before (another run's tables) or, in piece 0, receives
 //      the diagonal entry; the own block is computed in natural order and stored with lanes 0 .. R rotated by one position
 //      (lane R, whose diagonal entry belongs to position 0 of the ROW, carries the last column of the block before).
-// Status (round 4, profiles/r04_wg_variants.txt): parity green on blocks and staircase agglomerates in both layouts; 1.45-1.61 ms on
-// the bench mesh where pdh_rows.h takes 1.55-1.65 on the same boxes - within the spread between two allocations of the values, so
-// AUTO keeps pdh_rows.h and this kernel is taken on request (PDH_TERMS_DGQ3=1).  Without its stores it needs 1.02 ms (pdh_rows.h:
-// 0.86): the term form costs this element more VALU work than the moment form + MFMA contraction (8 000 against 5 900 instructions
-// per polytope), which eats what the shared store pattern gains.  A persistent variant that requests the next polytope's
-// descriptors and point data during phase B (raw s_barrier hand-offs, no vmcnt(0)) was measured equal at 156 VGPRs and 15 % slower
-// when held to 128: not kept.
+// Status: parity green on blocks and staircase agglomerates in both layouts.  The planner's DEFAULT for FE_DGQ(3) wherever the term
+// tables can be built (plan_kernels in pdh_plan.cpp; PDH_TERMS_DGQ3=0 or PDH_TERMS=0 keeps pdh_rows.h), since the records of 1-D rules
+// and the merged cells: 1.28-1.35 ms on the bench mesh where pdh_rows.h takes 1.59-1.66, never slower on the other shapes tried
+// (profiles/r04_wg_forms.txt; the first version, profiles/r04_wg_variants.txt, was 1.45-1.61 against 1.55-1.65 - within the spread
+// between two allocations of the values - and ran on request only).  Measured on that first version: without its stores it needs
+// 1.02 ms (pdh_rows.h: 0.86) - the term form costs this element more VALU work than the moment form + MFMA contraction (8 000 against
+// 5 900 instructions per polytope); a persistent variant that requests the next polytope's descriptors and point data during phase B
+// (raw s_barrier hand-offs, no vmcnt(0)) was equal at 156 VGPRs and 15 % slower when held to 128: not kept.
 #pragma once
 #include "pdh_terms.h"
-
-#ifndef PDHW_STORE_AUX
-#define PDHW_STORE_AUX 2 // gfx940+ cache-policy bits of the row stores: 1 = sc0, 2 = nt, 16 = sc1 (nt alone: 1.48-1.52 ms where sc1|nt, the
-                         // policy of pdh_rows.h, gives 1.51-1.61, profiles/r04_wg_variants.txt)
-#endif
 
 // -DPDHT_STAMP (diagnostic builds): cycle counter of wave w at four points -> stamps[slot][4 w + k] (W = 4 only)
 #ifdef PDHT_STAMP
@@ -46,6 +42,10 @@
 
 namespace pdht
 {
+// gfx940+ cache-policy bits of the row stores: 1 = sc0, 2 = nt, 16 = sc1 (nt alone: 1.48-1.52 ms where sc1|nt, the policy of
+// pdh_rows.h, gives 1.51-1.61, profiles/r04_wg_variants.txt)
+constexpr int WG_STORE_AUX = 2;
+
 template <int W, bool SHIFTED, int PMAX>
 __global__ void __launch_bounds__(PDH_WAVE *W, 3) k_terms_wg(const PdhDev P, const PdhTerms T, const int n_owned)
 {
@@ -183,10 +183,7 @@ __global__ void __launch_bounds__(PDH_WAVE *W, 3) k_terms_wg(const PdhDev P, con
   const int first_int = nsfb > 0 ? 1 : 0;                     // the boundary run, if any, is run 0
   const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(P.values + rbase, 0, NF * rlen * 8, 0x00020000);
   auto row_store = [&](double v, uint32_t lane_bytes, uint32_t row_bytes) {
-#ifdef PDHW_NOSTORE
-    if (P.n < 0) // (experiment: everything computed, nothing stored)
-#endif
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, PDHW_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, WG_STORE_AUX);
   };
   const uint32_t row0_bytes = (uint32_t)R0 * (uint32_t)rlen * 8u, rstep = (uint32_t)rlen * 8u;
   // rows r = k0 + 4 i (i-th value of k1):  acc[r] += f0[k0] * (f1[i] * f2)
