@@ -344,7 +344,9 @@ int pdh_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y);
  * positive definite (a Cholesky pivot <= 0 or not finite) - for point Jacobi a zero or non-finite diagonal entry - makes the set-up
  * fail with PDH_EINVAL naming the first such polytope.  PDH_PREC_BLOCK_JACOBI needs n <= 64 dofs per polytope (PDH_EUNSUPPORTED).
  * pdh_precondition_device (z = P^-1 r over the owned rows, device pointers, asynchronous) and pdh_solve_cg* return PDH_ESTATE when
- * the values changed (pdh_set_problem*, pdh_assemble*, pdh_exchange_apply) since the set-up.  PDH_PREC_NONE needs no set-up call. */
+ * the values changed (pdh_set_problem*, pdh_assemble*, pdh_exchange_apply) since the set-up.  PDH_PREC_NONE needs no set-up call.
+ * d_r and d_z of pdh_precondition_device are either the same array (in place, every kind) or disjoint: a partial overlap is
+ * PDH_EINVAL.                                                                                                                        */
 #define PDH_PREC_NONE 0
 #define PDH_PREC_JACOBI 1       /* inverse of the diagonal                                */
 #define PDH_PREC_BLOCK_JACOBI 2 /* inverses of the n x n diagonal blocks, one per polytope */

@@ -178,6 +178,9 @@ extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *
   PDH_TRY(need_problem(ctx, "pdh_precondition_device"));
   if (!d_r || !d_z)
     return fail(ctx, PDH_EINVAL, "r and z are required");
+  // in place is served (a slot's r is read before its z is written); a shifted z would overwrite r of slots not read yet
+  if (d_r != d_z && overlap(d_r, ctx->prob.n_rows_owned, d_z, ctx->prob.n_rows_owned))
+    return fail(ctx, PDH_EINVAL, "r and z overlap partially (they must be the same array or disjoint)");
   PDH_TRY(prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   const PdhSolveArgs A = solve_args(ctx);

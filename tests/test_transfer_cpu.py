@@ -51,6 +51,33 @@ def test_children_are_in_ascending_fine_index(case):
         assert list(np.diff(ptr)) == [6, 2]
 
 
+@pytest.mark.parametrize("dim,n1d", tc.BOX_PAIRS, ids=lambda v: str(v))
+def test_box_cases_have_the_shape_they_are_listed_for(dim, n1d):
+    """one raw case per (dim, N1D) the kernels instantiate: children counts 1, 2, G + 3 (counts of both levels no multiples of G where
+    G > 1), children of a parent not contiguous, permuted offsets, every child a proper sub-box with a different 1-D matrix on every
+    axis; and the yardstick itself reproduces the degree-p polynomial far inside the 5e-13 the device test asks (degrees 5 .. 7 too)."""
+    c = tc.build(("raw", "boxes_%dd_n%d" % (dim, n1d)))
+    d, G = c.desc, tc.boxes_group(dim, n1d)
+    assert (d.dim, d.degree + 1, d.n) == (dim, n1d, n1d ** dim) and G == (64 // d.n if d.n < 64 else 1)
+    ptr, idx = d.children()
+    assert sorted(np.diff(ptr)) == [1, 2, G + 3] and d.n_coarse == 3 and d.n_fine == G + 6
+    if G > 1:  # (G = 2: G + 6 fine polytopes fill their waves; the coarse count still leaves an idle group)
+        assert (d.n_fine % G or G == 2) and d.n_coarse % G
+    assert np.any(np.diff(d.parent) < 0)  # the fine polytopes are not sorted by parent
+    assert not np.array_equal(d.fine_dof_offset, d.n * np.arange(d.n_fine)) and not np.array_equal(d.coarse_dof_offset, d.n * np.arange(3))
+    B = d.matrices_1d()
+    for a in range(dim):
+        for b in range(a):
+            assert np.min(np.max(np.abs(B[:, a] - B[:, b]), axis=(1, 2))) > 1e-3     # no two axes alike
+        assert np.min(np.max(np.abs(B[:, a] - B[:, a].transpose(0, 2, 1)), axis=(1, 2))) > 1e-4  # nor a factor symmetric
+    pc = d.coarse_bbox[d.parent]
+    assert np.all(d.fine_bbox[:, 0] > pc[:, 0]) and np.all(d.fine_bbox[:, 1] < pc[:, 1])
+    f = tc.poly(dim, d.degree)
+    err = float(np.max(np.abs(c.P @ tc.interpolate(d, "coarse", f) - tc.interpolate(d, "fine", f))))
+    print("boxes %dD N1D %d: interpolant error of the yardstick %.3e" % (dim, n1d, err))
+    assert err <= 5e-14
+
+
 def _variant(base, **over):
     """a copy of a description with some fields replaced"""
     kw = dict(dim=base.dim, degree=base.degree, basis=base.basis, fine_bbox=base.fine_bbox.copy(), coarse_bbox=base.coarse_bbox.copy(),

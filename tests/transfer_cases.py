@@ -17,7 +17,10 @@ PAIRS = [
     (3, 1, 2, 1, 1, 0.0),  # one coarse polytope
 ]
 RAW = ["uneven", "permuted", "permuted_2d"]
-CASES = [("pair",) + p for p in PAIRS] + [("raw", name) for name in RAW]
+# one raw description per (dim, N1D) pair the kernels instantiate (csrc/pdh_transfer.hip: launch_dim), see _boxes()
+BOX_PAIRS = [(dim, n1d) for dim in (2, 3) for n1d in range(2, 9)]
+RAW += ["boxes_%dd_n%d" % pair for pair in BOX_PAIRS]
+CASES =[("pair",) + p for p in PAIRS] + [("raw", name) for name in RAW]
 PERMUTED_BASE = (3, 2, 4, 2, 2, 0.1)     # (one coarse polytope: only the fine numbering can move)
 PERMUTED_2D_BASE = (2, 3, 4, 2, 1, 0.0)  # four coarse polytopes: both numberings move
 
@@ -143,6 +146,48 @@ def _permuted(base=PERMUTED_BASE):
                         fine_dof_offset=d.n * np.arange(d.n_fine)[::-1], coarse_dof_offset=coarse_off, parent=d.parent)
 
 
+def boxes_group(dim, n1d):
+    """G of csrc/pdh_transfer.hip's Cut: polytopes of fewer than 64 dofs that share a wave"""
+    return max(1, 64 // n1d ** dim)
+
+
+def _boxes(dim, n1d):
+    """Three coarse boxes inside the unit cube with a different extent on every axis and 1, 2 and G + 3 children: uneven children, and
+    fine and coarse counts that are no multiples of G (the kernels' idle groups, pol[g] = -1).  Every child is a proper sub-box of its
+    parent - the children need not tile it, the planner only asks that they lie inside - with its own offset and width on EACH axis
+    (fixed seed), so that every 1-D matrix of every child is a different full matrix: mixing up two axes or transposing a factor
+    changes the answer, which slabs along one axis (identity factors on the others) would not show.  The fine polytopes come in a
+    shuffled order (the children of a parent are not contiguous) and the dof offsets of both levels are permuted."""
+    from polydeal_amd._capi import TransferDesc
+
+    n, G = n1d ** dim, boxes_group(dim, n1d)
+    rng = np.random.default_rng(1000 * dim + n1d)
+    coarse = np.array([[[0.00, 0.00, 0.20], [0.30, 0.80, 0.90]],
+                       [[0.30, 0.10, 0.00], [0.55, 0.70, 0.50]],
+                       [[0.55, 0.25, 0.10], [1.00, 1.00, 1.00]]])[:, :, :dim]
+    parent = np.repeat(np.arange(3), [1, 2, G + 3])
+    parent = parent[rng.permutation(len(parent))]
+    ext = coarse[parent, 1] - coarse[parent, 0]
+
+    def apart(v):  # no two axes of a child alike
+        return min(float(np.abs(v[:, a] - v[:, b]).min()) for a in range(dim) for b in range(a)) > 1e-3
+    while True:  # (fixed seed: the same draw every time)
+        start = rng.uniform(0.05, 0.45, (len(parent), dim))  # as fractions of the parent's extent
+        width = rng.uniform(0.20, 0.50, (len(parent), dim))
+        if apart(start) and apart(width):
+            break
+    assert apart(ext)
+    lo = coarse[parent, 0] + start * ext
+    fine = np.stack([lo, lo + width * ext], axis=1)
+    def permutation(m):
+        while True:
+            p = rng.permutation(m)
+            if np.any(p != np.arange(m)):
+                return p
+    return TransferDesc(dim=dim, degree=n1d - 1, fine_bbox=fine, coarse_bbox=coarse, fine_dof_offset=n * permutation(len(parent)),
+                        coarse_dof_offset=n * permutation(3), parent=parent)
+
+
 class Case:
     def __init__(self, case):
         from polydeal_amd.handler import transfer_description
@@ -152,6 +197,8 @@ class Case:
         if case[0] == "pair":
             self.handlers, self.oracles = handler_pair(*case[1:])
             self.desc = transfer_description(*self.handlers)
+        elif case[1].startswith("boxes_"):
+            self.desc = _boxes(int(case[1][6]), int(case[1][10:]))
         else:
             self.desc = {"uneven": _uneven, "permuted": _permuted, "permuted_2d": lambda: _permuted(PERMUTED_2D_BASE)}[case[1]]()
         self._P = None
