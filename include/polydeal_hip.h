@@ -462,6 +462,53 @@ int pdh_restrict_and_add_device  (pdh_transfer *t, const double *d_fine,   doubl
 int pdh_prolongate(pdh_transfer *t, const double *coarse, double *fine);
 int pdh_restrict  (pdh_transfer *t, const double *fine,   double *coarse);
 
+/* Dense direct solve on the resident matrix (pdh_dense.hip): the coarse solver of a multigrid hierarchy, the reference's MGCoarseDirect
+ * (examples/simplex_agglomerated_multigrid.cc:71-100, used at :476).  For a context that owns all rows with PDH_EXCHANGE_NONE (else PDH_EUNSUPPORTED,
+ * like pdh_setup_chebyshev) and has at most 1024 rows (more: PDH_EUNSUPPORTED; 1024 rows are 16 polytopes of 64 dofs).  The set-up runs on
+ * the device without reading the matrix back: the resident rows are gathered into a dense array (the diagonal-first shift undone,
+ * dof_offset honoured), factored A = L L^T, and the explicit inverse G = L^-T L^-1 is stored EXACTLY symmetric; every sum has a fixed
+ * order.  A Cholesky pivot (the diagonal entry at its elimination step) <= 0 or not finite is PDH_EINVAL naming the row.  After a
+ * successful set-up PDH_PREC_DIRECT is the preconditioner of the context: pdh_precondition_device gives z = G r by one kernel queued on
+ * pdh_stream() (in place or disjoint, like every other kind; the same call on the same data gives the same bits), pdh_solve_cg* uses
+ * it, and the staleness rules of the other kinds apply (PDH_ESTATE once the values changed).  pdh_setup_preconditioner does not take
+ * PDH_PREC_DIRECT (PDH_EINVAL).                                                                                                       */
+#define PDH_PREC_DIRECT 4
+typedef struct pdh_direct_info
+{
+  int32_t n_rows;
+  double pivot_min, pivot_max; /* smallest / largest Cholesky pivot */
+} pdh_direct_info;
+int pdh_setup_direct(pdh_ctx *ctx, pdh_direct_info *info /* may be NULL */);
+
+/* Multigrid V-cycle over resident level matrices (pdh_capi_mg.cpp; no kernel of its own: the smoother, the residual, the transfers and
+ * the coarse solver above), the reference's Multigrid / PreconditionMG of examples/simplex_agglomerated_multigrid.cc:378-515.
+ * pdh_mg_create takes 2 <= n_levels <= 16 contexts, COARSE TO FINE, on one device, each owning all rows of an assembled problem; every
+ * level above the coarsest with PDH_PREC_CHEBYSHEV set up and current (its smoother), the coarsest with ANY preconditioner set up and
+ * current as its solver - PDH_PREC_DIRECT, or Chebyshev / block Jacobi / Jacobi beyond 1024 rows; PDH_PREC_NONE is refused.  Every kind
+ * is a fixed symmetric positive operator, so the cycle is one too.  transfers[l] connects level l and l + 1, was created on levels[l + 1]
+ * and has their row counts.  A violation is PDH_EINVAL or PDH_ESTATE with a message naming the level, reported on the FINEST context
+ * (pdh_last_error(levels[n_levels - 1])), as every later error of the mg is.  The mg owns the level vectors b_l, x_l, r_l; it
+ * synchronises every level's stream once and makes PDH_PREC_MULTIGRID the preconditioner of the finest context:
+ * pdh_precondition_device(finest, r, z) is one V-cycle from zero and pdh_solve_cg* on the finest context is V-cycle-preconditioned CG
+ * (the same solve gives the same bits).
+ *   One cycle, every launch of every level on pdh_stream(finest) as it stands at the call - no events, no second stream, no graph, no
+ *   host synchronisation, no read-back.  From the finest level l down: x_l <- Chebyshev on b_l (from zero; on the finest level from
+ *   the caller's x if zero_initial_guess == 0), r_l = b_l - A_l x_l, b_(l-1) = P^T r_l; x_0 = the coarsest preconditioner applied to
+ *   b_0; on the way up x_l += P x_(l-1), then Chebyshev from x_l.
+ * pdh_mg_vcycle_device: device pointers [n_rows of the finest level], b and x must not overlap (PDH_EINVAL).  A later
+ * pdh_setup_preconditioner / pdh_setup_chebyshev / pdh_setup_direct on the finest context replaces the preconditioner and detaches the
+ * mg; pdh_mg_destroy detaches it too - the context falls back to PDH_PREC_NONE and says so (PDH_ESTATE) when it is asked to
+ * precondition or solve before something is set up again.  Once the values or the preconditioner of ANY level changed since
+ * pdh_mg_create, every entry of the mg and pdh_precondition_device / pdh_solve_cg* on the finest context return PDH_ESTATE naming the
+ * level.  Destroy the mg before its transfers and contexts.                                                                          */
+#define PDH_PREC_MULTIGRID 5
+typedef struct pdh_mg pdh_mg;
+int  pdh_mg_create(int n_levels, pdh_ctx *const *levels /* coarse to fine */,
+                   pdh_transfer *const *transfers /* [n_levels-1]; transfers[l]: level l <-> l+1, created on levels[l+1] */,
+                   pdh_mg **out);
+void pdh_mg_destroy(pdh_mg *mg);
+int  pdh_mg_vcycle_device(pdh_mg *mg, const double *d_b, double *d_x, int zero_initial_guess);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

@@ -18,7 +18,7 @@ PDH_BASIS_DGQ = 0
 PDH_BASIS_AGGLODGP = 1
 PDH_OK = 0
 PDH_EINVAL, PDH_EUNSUPPORTED, PDH_EDEVICE, PDH_ESTATE, PDH_ENOCONV = -1, -2, -3, -4, -5
-PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI, PDH_PREC_CHEBYSHEV = 0, 1, 2, 3
+PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI, PDH_PREC_CHEBYSHEV, PDH_PREC_DIRECT, PDH_PREC_MULTIGRID = 0, 1, 2, 3, 4, 5
 _PREC = {"none": PDH_PREC_NONE, "jacobi": PDH_PREC_JACOBI, "block_jacobi": PDH_PREC_BLOCK_JACOBI}
 CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
@@ -47,6 +47,10 @@ class pdh_chebyshev_info(C.Structure):
                 ("degree", C.c_int32), ("inner", C.c_int32)]
 
 
+class pdh_direct_info(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("pivot_min", C.c_double), ("pivot_max", C.c_double)]
+
+
 class _Opaque(C.c_void_p):
     """A typed opaque handle: accepts None, an address, or any c_void_p holding one."""
 
@@ -61,6 +65,10 @@ class pdh_ctx_p(_Opaque):
 
 class pdh_transfer_p(_Opaque):
     """pdh_transfer *"""
+
+
+class pdh_mg_p(_Opaque):
+    """pdh_mg *"""
 
 
 class pdh_transfer_desc(C.Structure):
@@ -100,6 +108,7 @@ EXPORTS = [
     "pdh_residual_device", "pdh_check_transfer", "pdh_transfer_children", "pdh_transfer_create",
     "pdh_transfer_destroy", "pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device",
     "pdh_restrict_and_add_device", "pdh_prolongate", "pdh_restrict",
+    "pdh_setup_direct", "pdh_mg_create", "pdh_mg_destroy", "pdh_mg_vcycle_device",
 ]
 
 # (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
@@ -191,6 +200,11 @@ def _bind(lib):
     for name in ("pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device", "pdh_restrict_and_add_device",
                  "pdh_prolongate", "pdh_restrict"):
         getattr(lib, name).argtypes = [pdh_transfer_p, C.c_void_p, C.c_void_p]
+    lib.pdh_setup_direct.argtypes = [pdh_ctx_p, P(pdh_direct_info)]
+    lib.pdh_mg_create.argtypes = [C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+    lib.pdh_mg_destroy.argtypes = [pdh_mg_p]
+    lib.pdh_mg_destroy.restype = None
+    lib.pdh_mg_vcycle_device.argtypes = [pdh_mg_p, C.c_void_p, C.c_void_p, C.c_int]
     return real
 
 
@@ -364,6 +378,41 @@ class Transfer:
     def __del__(self):
         try:
             if self.ctx.h:  # a context closed first took the device with it: nothing to free through
+                self.close()
+        except Exception:
+            pass
+
+
+class Multigrid:
+    """pdh_mg wrapper: the V-cycle over `levels` (Contexts, coarse to fine, each with its assembled matrix; Chebyshev set up on every
+    level above the coarsest, any preconditioner - setup_direct - on the coarsest) and `transfers` (transfers[l] between level l and
+    l + 1, created on levels[l + 1]).  Creating it makes the cycle the preconditioner of the finest context: precondition_device and
+    solve_cg* there.  Errors are reported on the finest context.  Close it before its transfers and contexts."""
+
+    def __init__(self, levels, transfers):
+        self.levels, self.transfers = list(levels), list(transfers)
+        self.finest = self.levels[-1]
+        self.lib = self.finest.lib
+        lv = (C.c_void_p * len(self.levels))(*[c.h.value for c in self.levels])
+        tr = (C.c_void_p * max(len(self.transfers), 1))(*[t.h.value for t in self.transfers])
+        h = C.c_void_p()
+        self.h = None
+        self.finest._chk(self.lib.pdh_mg_create(len(self.levels), lv, tr, C.byref(h)))
+        self.h = h
+
+    def vcycle_device(self, d_b, d_x, zero_initial_guess=False):
+        """One V-cycle on x for the right-hand side b (device pointers as ints, the finest level's size), queued on the finest
+        context's stream."""
+        self.finest._chk(self.lib.pdh_mg_vcycle_device(self.h, C.c_void_p(d_b), C.c_void_p(d_x), int(bool(zero_initial_guess))))
+
+    def close(self):
+        if self.h:
+            self.lib.pdh_mg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.finest.h:  # (as Transfer: a context closed first took the device with it)
                 self.close()
         except Exception:
             pass
@@ -543,6 +592,13 @@ class Context:
         return {"estimate": float(info.estimate), "lambda_lo": float(info.lambda_lo), "lambda_hi": float(info.lambda_hi),
                 "cg_iterations": int(info.cg_iterations), "degree": int(info.degree),
                 "inner": {v: k for k, v in _PREC.items()}[int(info.inner)]}
+
+    def setup_direct(self):
+        """Dense direct solve (pdh_setup_direct: at most 1024 rows): the explicit inverse becomes the preconditioner of
+        precondition_device and solve_cg*.  Returns {n_rows, pivot_min, pivot_max}."""
+        info = pdh_direct_info()
+        self._chk(self.lib.pdh_setup_direct(self.h, C.byref(info)))
+        return {"n_rows": int(info.n_rows), "pivot_min": float(info.pivot_min), "pivot_max": float(info.pivot_max)}
 
     def chebyshev_step_device(self, d_b, d_x, zero_initial_guess=False):
         """One application of the smoother to b from the x in d_x (device pointers as ints); asynchronous on the context's stream."""

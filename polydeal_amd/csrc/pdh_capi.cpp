@@ -113,6 +113,7 @@ extern "C" void pdh_destroy(pdh_ctx *ctx)
     return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  pdh_mg_detach(ctx); // (a pdh_mg is destroyed before its contexts; one still attached here must not be reached through this one)
   free_problem(ctx);
   for (DevBuf *b : {&ctx->io.in0, &ctx->io.in1, &ctx->io.ptr, &ctx->io.out, &ctx->io.grad, &ctx->io.err, &ctx->shape_midx, &ctx->checksum})
     b->release(); // (before the streams go, as ever)

@@ -1,12 +1,14 @@
 // pdh_capi_solve.cpp — device driver of the C ABI, solving with the resident matrix (kernels: pdh_solve.hip): y = A x, the Jacobi /
 // block Jacobi inverses, CG, and the Chebyshev smoother / preconditioner.  The one CG recurrence (CgRun) serves the solver and the
-// eigenvalue estimate of the Chebyshev set-up; the host arithmetic of the latter is the planner's (pdh_plan.h).
+// eigenvalue estimate of the Chebyshev set-up; the host arithmetic of the latter is the planner's (pdh_plan.h).  The dense direct solve
+// (kernels: pdh_dense.hip) is one more preconditioner; the V-cycle (pdh_capi_mg.cpp) composes the helpers of this unit.
 #include "pdh_ctx.h"
+#include "pdh_dense.h"
 #include "pdh_launch.h"
 
 #include <cmath>
 
-static PdhSolveArgs solve_args(const pdh_ctx *ctx)
+PdhSolveArgs pdh_solve_args(const pdh_ctx *ctx)
 {
   PdhSolveArgs A;
   A.values = ctx->prob.dev.values;
@@ -31,7 +33,7 @@ static bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
 
 static constexpr int PDH_VMULT_LDS_CAP = 64 * 1024; // column set of one polytope in LDS (8192 columns)
 
-static int row_fits_lds(pdh_ctx *ctx)
+int pdh_row_fits_lds(pdh_ctx *ctx)
 {
   if ((int64_t)ctx->prob.max_row_len * (int64_t)sizeof(double) > PDH_VMULT_LDS_CAP)
     return fail(ctx, PDH_EUNSUPPORTED, "a row has more than 8192 entries (the column set of a polytope must fit 64 KB of LDS)");
@@ -59,14 +61,14 @@ static int vmult_checks(pdh_ctx *ctx, const void *x, const void *y)
     return fail(ctx, PDH_EINVAL, "x and y are required");
   if (overlap(x, ctx->prob.n_rows_total, y, ctx->prob.n_rows_owned))
     return fail(ctx, PDH_EINVAL, "x and y overlap");
-  return row_fits_lds(ctx);
+  return pdh_row_fits_lds(ctx);
 }
 
 extern "C" int pdh_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y)
 {
   PDH_TRY(vmult_checks(ctx, d_x, d_y));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  const PdhSolveArgs A = solve_args(ctx);
+  const PdhSolveArgs A = pdh_solve_args(ctx);
   PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, d_y, nullptr, ctx->stream));
   return PDH_OK;
 }
@@ -92,12 +94,21 @@ extern "C" int pdh_residual_device(pdh_ctx *ctx, const double *d_b, const double
     return fail(ctx, PDH_EINVAL, "b, x and r are required");
   if (overlap(d_x, ctx->prob.n_rows_total, d_r, ctx->prob.n_rows_owned) || overlap(d_b, ctx->prob.n_rows_owned, d_r, ctx->prob.n_rows_owned))
     return fail(ctx, PDH_EINVAL, "r overlaps x or b");
-  PDH_TRY(row_fits_lds(ctx));
+  PDH_TRY(pdh_row_fits_lds(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  const PdhSolveArgs A = solve_args(ctx);
+  const PdhSolveArgs A = pdh_solve_args(ctx);
   PDH_HIP(ctx, pdh_launch_vmult(&A, d_x, d_r, nullptr, ctx->stream));
   PDH_HIP(ctx, pdh_launch_residual_sub(ctx->prob.n_rows_owned, d_b, d_r, ctx->stream));
   return PDH_OK;
+}
+
+// every set-up call replaces the preconditioner: an attached V-cycle is let go of, and a pdh_mg that has this context as a level sees
+// the new epoch
+static void new_setup(pdh_ctx *ctx)
+{
+  pdh_mg_detach(ctx);
+  ctx->mg_gone = false;
+  ++ctx->prec_epoch;
 }
 
 extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
@@ -107,6 +118,7 @@ extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
     return fail(ctx, PDH_EINVAL, "kind must be PDH_PREC_NONE, PDH_PREC_JACOBI or PDH_PREC_BLOCK_JACOBI");
   if (kind == PDH_PREC_BLOCK_JACOBI && ctx->prob.dev.n > 64)
     return fail(ctx, PDH_EUNSUPPORTED, "block Jacobi needs at most 64 dofs per polytope (use PDH_PREC_JACOBI)");
+  new_setup(ctx);
   ctx->prec_kind = kind;
   ctx->prec_gen = ctx->values_gen;
   ctx->prec_ok = false; // until the set-up below has succeeded
@@ -122,7 +134,7 @@ extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
   int32_t *flag = S.flag.get<int32_t>(ctx->prob.n_owned);
   if (!dinv || !flag)
     return fail(ctx, PDH_EDEVICE, "pdh_setup_preconditioner: out of device memory");
-  const PdhSolveArgs A = solve_args(ctx);
+  const PdhSolveArgs A = pdh_solve_args(ctx);
   PDH_HIP(ctx, kind == PDH_PREC_BLOCK_JACOBI ? pdh_launch_block_inverse(&A, dinv, flag, ctx->stream)
                                              : pdh_launch_diag_inverse(&A, dinv, flag, ctx->stream));
   std::vector<int32_t> h_flag((size_t)ctx->prob.n_owned);
@@ -145,6 +157,11 @@ extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
 
 static int prec_checks(pdh_ctx *ctx)
 {
+  if (ctx->mg_gone)
+    return fail(ctx, PDH_ESTATE, "the multigrid preconditioner of this context was destroyed: the context fell back to PDH_PREC_NONE, set a "
+                                 "preconditioner up again (pdh_setup_preconditioner takes PDH_PREC_NONE)");
+  if (ctx->prec_kind == PDH_PREC_MULTIGRID)
+    return ctx->mg ? pdh_mg_checks(ctx->mg) : fail(ctx, PDH_ESTATE, "the multigrid preconditioner is not attached");
   if (ctx->prec_kind != PDH_PREC_NONE && (!ctx->prec_ok || ctx->prec_gen != ctx->values_gen))
     return fail(ctx, PDH_ESTATE, ctx->prec_ok ? "the values changed since pdh_setup_preconditioner: set it up again"
                                               : "the last pdh_setup_preconditioner failed");
@@ -153,23 +170,54 @@ static int prec_checks(pdh_ctx *ctx)
 
 // One application of the Chebyshev polynomial to b, queued on the stream: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b,
 // x not read).  d, r and q are the context's own vectors - never CG's residual.  rcg / part: see pdh_launch_cheb_update.
-static int cheb_apply(pdh_ctx *ctx, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part)
+int pdh_cheb_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part,
+                   hipStream_t stream)
 {
   const pdh_ctx::Problem::Solver &S = ctx->prob.sol;
   double *d = S.cheb_d.ptr<double>(), *r = S.cheb_r.ptr<double>(), *q = S.q.ptr<double>();
   const double *dinv = S.dinv.ptr<double>();
   const int m = (int)S.cheb_c2.size();
   if (!d || !r || !q || !dinv || m < 1)
-    return fail(ctx, PDH_ESTATE, "the Chebyshev preconditioner is not set up");
+    return fail(report, PDH_ESTATE, "the Chebyshev preconditioner is not set up");
   if (!zero)
-    PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, ctx->stream));
+    PDH_HIP(report, pdh_launch_vmult(&A, x, q, nullptr, stream));
   for (int k = 0; k < m; ++k)
     {
       if (k > 0)
-        PDH_HIP(ctx, pdh_launch_vmult(&A, d, q, nullptr, ctx->stream));
-      PDH_HIP(ctx, pdh_launch_cheb_update(&A, k == 0, S.cheb_inner, dinv, b, (k == 0 && zero) ? nullptr : q, d, r, x, S.cheb_c1[k], S.cheb_c2[k],
-                                          k == 0 && zero, k == m - 1 ? rcg : nullptr, part, ctx->stream));
+        PDH_HIP(report, pdh_launch_vmult(&A, d, q, nullptr, stream));
+      PDH_HIP(report, pdh_launch_cheb_update(&A, k == 0, S.cheb_inner, dinv, b, (k == 0 && zero) ? nullptr : q, d, r, x, S.cheb_c1[k], S.cheb_c2[k],
+                                             k == 0 && zero, k == m - 1 ? rcg : nullptr, part, stream));
     }
+  return PDH_OK;
+}
+
+static int cheb_apply(pdh_ctx *ctx, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part)
+{
+  return pdh_cheb_apply(ctx, ctx, A, b, x, zero, rcg, part, ctx->stream);
+}
+
+// z = G r of PDH_PREC_DIRECT (r and z disjoint)
+static int direct_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *r, double *z, const double *rcg, double *part,
+                        hipStream_t stream)
+{
+  const pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (!S.dense_g.ptr<double>() || S.dense_n != ctx->prob.n_rows_owned)
+    return fail(report, PDH_ESTATE, "the direct solve is not set up");
+  PDH_HIP(report, pdh_launch_dense_symv(&A, S.dense_g.ptr<double>(), S.dense_ld, S.dense_n, r, z, rcg, part, stream));
+  return PDH_OK;
+}
+
+int pdh_prec_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *r, double *z, const double *rcg, double *part,
+                   hipStream_t stream)
+{
+  if (ctx->prec_kind == PDH_PREC_CHEBYSHEV)
+    return pdh_cheb_apply(ctx, report, A, r, z, true, rcg, part, stream);
+  if (ctx->prec_kind == PDH_PREC_DIRECT)
+    return direct_apply(ctx, report, A, r, z, rcg, part, stream);
+  if (rcg)
+    return fail(report, PDH_EINVAL, "pdh_prec_apply: no partials from this kind");
+  PDH_HIP(report, pdh_launch_cg_update(&A, PDH_UPD_APPLY, ctx->prec_kind, ctx->prob.sol.dinv.ptr<double>(), nullptr, nullptr, nullptr, nullptr,
+                                       const_cast<double *>(r), z, nullptr, nullptr, stream));
   return PDH_OK;
 }
 
@@ -183,33 +231,45 @@ extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *
     return fail(ctx, PDH_EINVAL, "r and z overlap partially (they must be the same array or disjoint)");
   PDH_TRY(prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  const PdhSolveArgs A = solve_args(ctx);
-  if (ctx->prec_kind == PDH_PREC_CHEBYSHEV)
-    return cheb_apply(ctx, A, d_r, d_z, true, nullptr, nullptr);
-  PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_APPLY, ctx->prec_kind, ctx->prob.sol.dinv.ptr<double>(), nullptr, nullptr,
-                                    nullptr, nullptr, const_cast<double *>(d_r), d_z, nullptr, nullptr, ctx->stream));
-  return PDH_OK;
+  const PdhSolveArgs A = pdh_solve_args(ctx);
+  if (ctx->prec_kind == PDH_PREC_DIRECT || ctx->prec_kind == PDH_PREC_MULTIGRID)
+    { // every wave reads all of r (the cycle: r again after z was written): the in-place call works on a copy of r
+      const int64_t N = ctx->prob.n_rows_owned;
+      if (d_r == d_z)
+        {
+          double *tmp = ctx->prob.sol.dense_tmp.get<double>((size_t)N);
+          if (!tmp)
+            return fail(ctx, PDH_EDEVICE, "pdh_precondition_device: out of device memory");
+          PDH_HIP(ctx, hipMemcpyAsync(tmp, d_r, N * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+          d_r = tmp;
+        }
+      if (ctx->prec_kind == PDH_PREC_MULTIGRID)
+        return pdh_mg_cycle(ctx->mg, d_r, d_z, true, nullptr, nullptr);
+      return direct_apply(ctx, ctx, A, d_r, d_z, nullptr, nullptr, ctx->stream);
+    }
+  return pdh_prec_apply(ctx, ctx, A, d_r, d_z, nullptr, nullptr, ctx->stream);
 }
 
 // The preconditioned CG recurrence on the resident matrix, queued on the context's stream: the loop of examples/host_solver.h (q = A p,
 // alpha, x and r, z, beta, p) with every scalar kept on the device.  After each of start() / step() `n_scalars` doubles from
 // scal[first_scalar] are in ctx->pinned and the stream is idle - what they are and what follows from them is the caller's.
-// kind: the preconditioner of the fused update; chain: the Chebyshev chain z = p(P^-1 A) P^-1 r follows it instead (kind none leaves z
-// alone), its last step writes the partials of r^T z.
+// kind: the preconditioner of the fused update; chain: an application z = M r queued after it instead (kind none leaves z alone) -
+// the Chebyshev chain p(P^-1 A) P^-1, the dense inverse or the V-cycle attached to the context - whose last kernel writes the partials
+// of r^T z.
 struct CgRun
 {
   pdh_ctx *ctx;
   const PdhSolveArgs A;
   const int kind;
-  const bool chain;
+  const int chain; // PDH_PREC_NONE (no chain) | PDH_PREC_CHEBYSHEV | PDH_PREC_DIRECT | PDH_PREC_MULTIGRID
   const int64_t N;
   const int n_owned;
   hipStream_t st;
   double *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *part = nullptr, *scal = nullptr;
   const double *dinv = nullptr;
 
-  CgRun(pdh_ctx *c, int kind_, bool chain_)
-    : ctx(c), A(solve_args(c)), kind(kind_), chain(chain_), N(c->prob.n_rows_owned), n_owned(c->prob.n_owned), st(c->stream)
+  CgRun(pdh_ctx *c, int kind_, int chain_)
+    : ctx(c), A(pdh_solve_args(c)), kind(kind_), chain(chain_), N(c->prob.n_rows_owned), n_owned(c->prob.n_owned), st(c->stream)
   {
     pdh_ctx::Problem::Solver &S = c->prob.sol;
     r = S.r.get<double>(N), z = S.z.get<double>(N), p = S.p.get<double>(N), q = S.q.get<double>(N);
@@ -220,6 +280,12 @@ struct CgRun
     dinv = S.dinv.ptr<double>();
   }
   bool ok() const { return r && z && p && q && part && scal && ctx->pinned; }
+  int apply_chain()
+  {
+    if (chain == PDH_PREC_MULTIGRID)
+      return pdh_mg_cycle(ctx->mg, r, z, true, r, part);
+    return chain == PDH_PREC_NONE ? PDH_OK : pdh_prec_apply(ctx, ctx, A, r, z, r, part, st);
+  }
   int read_back(int first_scalar, int n_scalars)
   {
     PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + first_scalar, n_scalars * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -231,8 +297,7 @@ struct CgRun
   {
     PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, st));
     PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, b, q, nullptr, nullptr, r, z, scal, part, st));
-    if (chain)
-      PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
+    PDH_TRY(apply_chain());
     PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 0, scal, st));
     PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
     return read_back(first_scalar, n_scalars);
@@ -242,8 +307,7 @@ struct CgRun
     PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * n_owned, st));
     PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 1, scal, st));
     PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, x, r, z, scal, part, st));
-    if (chain)
-      PDH_TRY(cheb_apply(ctx, A, r, z, true, r, part));
+    PDH_TRY(apply_chain());
     PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 2, scal, st));
     PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
     return read_back(first_scalar, n_scalars);
@@ -261,10 +325,10 @@ extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const 
   if (overlap(d_b, ctx->prob.n_rows_total, d_x, ctx->prob.n_rows_total))
     return fail(ctx, PDH_EINVAL, "b and x overlap");
   PDH_TRY(prec_checks(ctx));
-  PDH_TRY(row_fits_lds(ctx));
+  PDH_TRY(pdh_row_fits_lds(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  const bool cheb = ctx->prec_kind == PDH_PREC_CHEBYSHEV;
-  CgRun cg(ctx, cheb ? PDH_PREC_NONE : ctx->prec_kind, cheb);
+  const bool chained = ctx->prec_kind == PDH_PREC_CHEBYSHEV || ctx->prec_kind == PDH_PREC_DIRECT || ctx->prec_kind == PDH_PREC_MULTIGRID;
+  CgRun cg(ctx, chained ? PDH_PREC_NONE : ctx->prec_kind, chained ? ctx->prec_kind : PDH_PREC_NONE);
   if (!cg.ok())
     return fail(ctx, PDH_EDEVICE, "pdh_solve_cg: out of device memory");
   PDH_TRY(cg.start(d_b, d_x, PDH_CG_RR, 2));
@@ -317,7 +381,7 @@ extern "C" int pdh_solve_cg(pdh_ctx *ctx, const pdh_cg_control *c, const double 
 static int cheb_estimate(pdh_ctx *ctx, int kind, int k, double *est, int *steps)
 {
   const int64_t N = ctx->prob.n_rows_owned;
-  CgRun cg(ctx, kind, false);
+  CgRun cg(ctx, kind, PDH_PREC_NONE);
   double *d_b = ctx->io.in0.get<double>((size_t)N), *d_x = ctx->io.in1.get<double>((size_t)N);
   if (!cg.ok() || !d_b || !d_x)
     return fail(ctx, PDH_EDEVICE, "pdh_setup_chebyshev: out of device memory");
@@ -370,7 +434,7 @@ extern "C" int pdh_setup_chebyshev(pdh_ctx *ctx, const pdh_chebyshev_control *c,
   if (!given && (c->eig_cg_n_iterations < 1 || c->eig_cg_n_iterations > 256))
     return fail(ctx, PDH_EINVAL, "pdh_setup_chebyshev: eig_cg_n_iterations must be 1 .. 256 (or give max_eigenvalue > 0)");
   PDH_TRY(all_rows_checks(ctx, "pdh_setup_chebyshev", "it needs", "it", ""));
-  PDH_TRY(row_fits_lds(ctx));
+  PDH_TRY(pdh_row_fits_lds(ctx));
   PDH_TRY(pdh_setup_preconditioner(ctx, c->inner)); // the inner inverse; prec_kind = inner for the estimate
   ctx->prec_ok = false;                             // until the whole set-up has succeeded
   PDH_HIP(ctx, hipSetDevice(ctx->device));
@@ -413,5 +477,56 @@ extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double
     return fail(ctx, PDH_ESTATE, "pdh_chebyshev_step_device: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
   PDH_TRY(prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  return cheb_apply(ctx, solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
+  return cheb_apply(ctx, pdh_solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
+}
+
+// ---- dense direct solve (include/polydeal_hip.h: pdh_setup_direct; steps and layout: pdh_dense.h) ---------------------------------------
+extern "C" int pdh_setup_direct(pdh_ctx *ctx, pdh_direct_info *info)
+{
+  PDH_TRY(need_problem(ctx, "pdh_setup_direct"));
+  PDH_TRY(all_rows_checks(ctx, "pdh_setup_direct", "it needs", "it", ""));
+  const int64_t N = ctx->prob.n_rows_owned;
+  if (N > PDH_DENSE_MAX_ROWS)
+    return fail(ctx, PDH_EUNSUPPORTED, "pdh_setup_direct: the problem has " + std::to_string(N) + " rows, the dense direct solve takes at most " +
+                                         std::to_string(PDH_DENSE_MAX_ROWS));
+  if (N < 1)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_direct: the problem has no rows");
+  new_setup(ctx);
+  ctx->prec_kind = PDH_PREC_DIRECT;
+  ctx->prec_gen = ctx->values_gen;
+  ctx->prec_ok = false; // until the set-up below has succeeded
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  const int ld = pdh_dense_ld(N);
+  const size_t nn = (size_t)ld * ld;
+  DevBuf work; // U, Wd, dg [ld], piv [2]: gone when the set-up returns
+  double *G = S.dense_g.get<double>(nn), *U = work.get<double>(2 * nn + ld + 2);
+  int32_t *flag = S.flag.get<int32_t>((size_t)std::max(ctx->prob.n_owned, 1));
+  if (!G || !U || !flag)
+    return fail(ctx, PDH_EDEVICE, "pdh_setup_direct: out of device memory");
+  double *Wd = U + nn, *dg = Wd + nn, *piv = dg + ld;
+  S.dense_ld = ld;
+  S.dense_n = (int)N;
+  const PdhSolveArgs A = pdh_solve_args(ctx);
+  PDH_HIP(ctx, hipMemsetAsync(U, 0, nn * sizeof(double), ctx->stream));
+  PDH_HIP(ctx, pdh_launch_dense_gather(&A, U, ld, (int)N, ctx->stream));
+  PDH_HIP(ctx, pdh_launch_dense_cholesky(U, ld, (int)N, dg, piv, flag, ctx->stream));
+  int32_t h_flag = 0;
+  double h_piv[2] = {0.0, 0.0};
+  PDH_HIP(ctx, hipMemcpyAsync(&h_flag, flag, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipMemcpyAsync(h_piv, piv, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (h_flag)
+    return fail(ctx, PDH_EINVAL, "pdh_setup_direct: the matrix is not positive definite (the Cholesky pivot of row " + std::to_string(h_flag - 1) +
+                                   " is <= 0 or not finite)");
+  PDH_HIP(ctx, pdh_launch_dense_inverse(U, dg, ld, (int)N, Wd, G, ctx->stream));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `work` is freed on return
+  ctx->prec_ok = true;
+  if (info)
+    {
+      info->n_rows = (int32_t)N;
+      info->pivot_min = h_piv[0];
+      info->pivot_max = h_piv[1];
+    }
+  return PDH_OK;
 }

@@ -66,6 +66,20 @@ extern "C" void pdh_transfer_destroy(pdh_transfer *t)
   delete t;
 }
 
+// for the V-cycle (pdh_capi_mg.cpp): what a transfer connects, and one of its launches on a stream of the caller's
+void pdh_transfer_info(const pdh_transfer *t, pdh_ctx **ctx, int64_t *n_fine_rows, int64_t *n_coarse_rows)
+{
+  *ctx = t->ctx;
+  *n_fine_rows = t->n_fine_rows;
+  *n_coarse_rows = t->n_coarse_rows;
+}
+
+hipError_t pdh_transfer_launch(const pdh_transfer *t, bool restriction, int add, const double *src, double *dst, hipStream_t stream)
+{
+  return restriction ? pdh_launch_restrict(t->dim, t->n1d, add, &t->args, src, dst, stream)
+                     : pdh_launch_prolongate(t->dim, t->n1d, add, &t->args, src, dst, stream);
+}
+
 static bool overlap(const void *a, int64_t na, const void *b, int64_t nb)
 {
   const char *pa = static_cast<const char *>(a), *pb = static_cast<const char *>(b);

@@ -1,4 +1,5 @@
-// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_transfer.cpp), not installed: the context
+// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_transfer.cpp, pdh_capi_mg.cpp), not
+// installed: the context
 // behind the opaque pdh_ctx of include/polydeal_hip.h, error reporting, the one device-buffer type, the alloc / upload helpers of
 // set-up and the entry guards.  No kernel header here: pdh_launch.h brings the kernels' argument structs and the launch records.
 #pragma once
@@ -92,6 +93,11 @@ struct pdh_ctx
   uint64_t values_gen = 0, prec_gen = 0;
   int prec_kind = PDH_PREC_NONE;
   bool prec_ok = true;
+  // prec_epoch counts the set-up calls (a pdh_mg records it per level: the same kind set up again on the same values is a change too);
+  // mg: the V-cycle attached as PDH_PREC_MULTIGRID (pdh_capi_mg.cpp), mg_gone: it was destroyed and nothing was set up since
+  uint64_t prec_epoch = 0;
+  struct pdh_mg *mg = nullptr;
+  bool mg_gone = false;
   // staging copies of the host-pointer entry points, shared by all of them: in0 f_vol / solution / bbox / x / b, in1 g_bdry / pts /
   // y / x, ptr pt_ptr (pdh_assemble_rhs: the rhs), out u / exact_u | w / shape values, grad grad / exact_grad, err the error sums
   struct Io
@@ -171,6 +177,10 @@ struct pdh_ctx
       DevBuf dinv, flag, r, z, p, q, part, scal, cheb_d, cheb_r;
       int cheb_inner = PDH_PREC_NONE;
       std::vector<double> cheb_c1, cheb_c2;
+      // PDH_PREC_DIRECT (pdh_dense.h): the inverse G [dense_ld][dense_ld] of the dense_n rows; dense_tmp: the copy of r of the in-place
+      // apply
+      DevBuf dense_g, dense_tmp;
+      int dense_ld = 0, dense_n = 0;
     } sol;
   } prob;
 
@@ -330,3 +340,26 @@ struct Staging
     return upload_in(ctx, bufs, h, count, dptr, what);
   }
 };
+
+// ---- what the driver units call of each other ----
+// pdh_capi_solve.cpp.  The launch helpers take the stream they queue on: the context's own for its entry points, the finest level's
+// for every level of a V-cycle.
+PdhSolveArgs pdh_solve_args(const pdh_ctx *ctx);
+int pdh_row_fits_lds(pdh_ctx *ctx); // PDH_EUNSUPPORTED on `ctx`: a row of more than 8192 entries (k_vmult keeps a column set in LDS)
+// One application of the Chebyshev polynomial of `ctx` to b: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b, x not read).
+// rcg / part: see pdh_launch_cheb_update.  Errors are reported on `report`.
+int pdh_cheb_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part,
+                   hipStream_t stream);
+// z = P^-1 r with the preconditioner of `ctx` as set up - any kind but PDH_PREC_MULTIGRID, r and z disjoint - without the state checks
+int pdh_prec_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *r, double *z, const double *rcg, double *part,
+                   hipStream_t stream);
+// pdh_capi_transfer.cpp
+void pdh_transfer_info(const pdh_transfer *t, pdh_ctx **ctx, int64_t *n_fine_rows, int64_t *n_coarse_rows);
+hipError_t pdh_transfer_launch(const pdh_transfer *t, bool restriction, int add, const double *src, double *dst, hipStream_t stream);
+// pdh_capi_mg.cpp: the V-cycle attached to a finest context.  pdh_mg_checks: PDH_ESTATE naming the level whose values or
+// preconditioner changed since pdh_mg_create; pdh_mg_cycle: one cycle queued on the finest context's stream, no checks (rcg / part: the
+// last post-smoothing update on the finest level writes the partials of rcg^T x); pdh_mg_detach: the context's set-up calls and
+// pdh_destroy let go of an attached mg.
+int pdh_mg_checks(pdh_mg *mg);
+int pdh_mg_cycle(pdh_mg *mg, const double *b, double *x, bool zero, const double *rcg, double *part);
+void pdh_mg_detach(pdh_ctx *ctx);

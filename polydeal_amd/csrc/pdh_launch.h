@@ -144,6 +144,18 @@ hipError_t pdh_launch_cg_direction(int64_t n_rows, int init, const double *z, do
 // one workgroup: partials -> scalars.  stage 0: rz, rr, bb;  1: pq, alpha;  2: rz, rr, beta
 hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, int stage, double *scal, hipStream_t stream);
 
+// pdh_dense.hip (pdh_dense.h: ld = pdh_dense_ld(n_rows), 1 <= n_rows <= PDH_DENSE_MAX_ROWS, else hipErrorInvalidValue)
+// D [ld][ld] (zeroed by the caller) = the resident rows, dense
+hipError_t pdh_launch_dense_gather(const PdhSolveArgs *A, double *D, int ld, int n_rows, hipStream_t stream);
+// Cholesky in the upper triangle of U = D, diagonal of L to dg [ld]; piv [2]: smallest / largest pivot, flag [1]: 0 or 1 + the row whose
+// pivot is <= 0 or not finite
+hipError_t pdh_launch_dense_cholesky(double *U, int ld, int n_rows, double *dg, double *piv, int32_t *flag, hipStream_t stream);
+// Wd [ld][ld] = L^-1, then G [ld][ld] = Wd^T Wd, exactly symmetric
+hipError_t pdh_launch_dense_inverse(const double *U, const double *dg, int ld, int n_rows, double *Wd, double *G, hipStream_t stream);
+// z = G r over the owned rows (r and z disjoint); rcg (may be NULL): partial of rcg^T z to PDH_PART_RZ
+hipError_t pdh_launch_dense_symv(const PdhSolveArgs *A, const double *G, int ld, int n_rows, const double *r, double *z,
+                                 const double *rcg, double *part, hipStream_t stream);
+
 // pdh_transfer.hip (dim 2 | 3, n1d 2 .. 8; add: accumulate into the destination)
 // fine (+)= P coarse: one wave per max(1, 64 / n) fine polytopes
 hipError_t pdh_launch_prolongate(int dim, int n1d, int add, const PdhTransferArgs *A, const double *coarse, double *fine, hipStream_t stream);

@@ -88,3 +88,75 @@ def two_grid_cycle_device(fine_ctx, coarse_ctx, transfer, d_b, d_x, d_r, d_rc, d
     transfer.prolongate_and_add_device(d_ec, d_x)
     fine_ctx.chebyshev_step_device(d_b, d_x)
     return info
+
+
+class MultigridHierarchy:
+    """What multigrid_hierarchy returns: the level contexts (coarse to fine, each with its assembled matrix), the transfers between
+    them and the _capi.Multigrid whose V-cycle is the preconditioner of the finest context.  `info`: per level, what its set-up
+    reported (setup_direct on level 0, setup_chebyshev above)."""
+
+    def __init__(self, contexts, transfers, mg, info):
+        self.contexts, self.transfers, self.mg, self.info = contexts, transfers, mg, info
+        self.finest = contexts[-1]
+
+    def solve_cg(self, b, x0=None, rel_tol=1e-13, abs_tol=0.0, max_iter=None):
+        """V-cycle-preconditioned CG on the finest level (Context.solve_cg): (x, info)"""
+        return self.finest.solve_cg(b, x0, rel_tol, abs_tol, max_iter)
+
+    def solve_cg_device(self, d_b, d_x, rel_tol=1e-13, abs_tol=0.0, max_iter=None):
+        return self.finest.solve_cg_device(d_b, d_x, rel_tol, abs_tol, max_iter)
+
+    def vcycle_device(self, d_b, d_x, zero_initial_guess=False):
+        self.mg.vcycle_device(d_b, d_x, zero_initial_guess)
+
+    def close(self):
+        """the mg first, then the transfers, then their contexts"""
+        if self.mg is not None:
+            self.mg.close()
+            self.mg = None
+        for t in self.transfers:
+            t.close()
+        self.transfers = []
+        for c in self.contexts:
+            c.close()
+        self.contexts = []
+
+
+def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = None, diag_first=True, degree=3, inner=None, device=0):
+    """The reference's agglomerated multigrid (examples/simplex_agglomerated_multigrid.cc:378-515) on one device: one context per level
+    handler of `levels` (coarse to fine, e.g. block_hierarchy's), each assembled like assemble_levels does (the Cartesian description
+    where it is taken); Chebyshev of `degree` over `inner` ('block_jacobi' up to 64 dofs per polytope, 'jacobi' above, unless given) as
+    the smoother of every level above the coarsest, the dense direct solve on the coarsest (at most 1024 rows), the level transfers
+    and the V-cycle, which becomes the preconditioner of the finest context.  Returns a MultigridHierarchy; close() it."""
+    from ._capi import Context, Multigrid, PdhError
+    from .handler import HostError
+
+    variant = variant or SipVariant.assemble_dg_matrix()
+    if inner is None:
+        inner = "block_jacobi" if fe.n_dofs_per_cell <= 64 else "jacobi"
+    contexts, transfers, info, mg = [], [], [], None
+    try:
+        for l, ah in enumerate(levels):
+            if fe != ah.fe:
+                raise ValueError("FE passed to multigrid_hierarchy differs from a level handler's")
+            ctx = Context(device)
+            contexts.append(ctx)
+            flat = None
+            if ah.grid.dim == 3:
+                try:
+                    flat = ah.flatten_cartesian(variant, diag_first, False)
+                    ctx.set_problem(flat)
+                except (PdhError, HostError):
+                    flat = None
+            if flat is None:
+                flat = ah.flatten(variant, diag_first, False)  # (no colind: nothing here reads the pattern back)
+                ctx.set_problem(flat)
+            ctx.assemble_device()
+            info.append(ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree))
+            if l > 0:
+                transfers.append(level_transfer(ctx, levels[l - 1], ah))
+        mg = Multigrid(contexts, transfers)
+    except Exception:
+        MultigridHierarchy(contexts, transfers, mg, info).close()
+        raise
+    return MultigridHierarchy(contexts, transfers, mg, info)

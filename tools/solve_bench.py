@@ -20,6 +20,14 @@ mesh, each level assembled in a context of its own.  prolongate, restrict and re
 each call must move (vectors + 1-D tables + index arrays; residual: the values + three vectors) and the resulting GB/s.  The one
 condition (field transfer_pair_under_cheb_update): prolongate + restrict together take less than one k_cheb_update on the fine level,
 measured in the same process.
+
+V-cycle section (--vcycle, alone; pdh_setup_direct, pdh_mg_create), written to profiles/r09_vcycle.json unless --out says otherwise: the
+hierarchy of the headline mesh (64^3 cells, FE_DGQ(3), polytopes of 32^3, 16^3, 8^3, 4^3 and 2^3 cells: 8 .. 32 768 polytopes, a coarsest
+level of 512 rows) built by levels.multigrid_hierarchy, every level resident in a context of its own.  (a) pdh_setup_direct on the
+coarsest level (wall time, it synchronises) and k_dense_symv alone (HIP events); (b) one V-cycle at smoother degree 3 and the same
+launches restricted to the finest level (pre-smoothing from zero, residual, post-smoothing), both by HIP events in the same process -
+their difference is what the coarser levels cost; (c) the solve b = A x*, rel_tol 1e-13, with block Jacobi and with the V-cycle at
+smoother degrees 2, 3 and 5: iterations, products with the finest A, seconds.  No condition is checked: the table is the result.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -247,6 +255,93 @@ def transfer_case(pa, torch, cells, p, reps):
     return rec
 
 
+def vcycle_case(pa, torch, cells, reps):
+    """the V-cycle figures: see the module docstring"""
+    from polydeal_amd._capi import Multigrid
+    from polydeal_amd.levels import block_hierarchy, multigrid_hierarchy
+
+    t0 = time.time()
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    fe = pa.FE_DGQ(3, 3)
+    blocks = [b for b in (32, 16, 8, 4, 2) if 2 * b <= cells]
+    handlers = block_hierarchy(grid, fe, blocks)
+    print("handlers of %d levels: %.1f s" % (len(blocks), time.time() - t0), flush=True)
+    hier = multigrid_hierarchy(handlers, fe, pa.SipVariant.poisson_example(fe), diag_first=True, degree=3)
+    print("hierarchy resident: %.1f s" % (time.time() - t0), flush=True)
+    stream = torch.cuda.current_stream().cuda_stream
+    for c in hier.contexts:
+        c.set_stream(stream)
+    fin, coarse = hier.finest, hier.contexts[0]
+    N, Nc = handlers[-1].n_dofs, handlers[0].n_dofs
+    vec = lambda n: torch.rand(n, dtype=torch.float64, device="cuda")
+    values = [c.stats()["n_values"] for c in hier.contexts]
+    est = [i.get("estimate") for i in hier.info]
+    out = {"element": "FE_DGQ(3)", "cells_per_axis": cells, "blocks": blocks, "polytopes": [h.n_agglomerates for h in handlers],
+           "rows": [h.n_dofs for h in handlers], "n_values": values, "level_matrix_bytes": 8.0 * sum(values),
+           "coarser_levels_over_finest_bytes": sum(values[:-1]) / values[-1]}
+    # (a) the direct solve of the coarsest level
+    hier.mg.close()
+    hier.mg = None
+    t = []
+    for _ in range(reps + 1):
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        info = coarse.setup_direct()
+        t.append((time.perf_counter() - w0) * 1e3)
+    rc, zc = vec(Nc), vec(Nc)
+    sy = event_times_ms(torch, lambda: coarse.precondition_device(rc.data_ptr(), zc.data_ptr()), reps)
+    out.update(direct_rows=Nc, direct_setup_wall_ms_median=median(t[1:]), direct_setup_wall_ms_min=min(t[1:]), direct_pivot_min=info["pivot_min"],
+               direct_pivot_max=info["pivot_max"], dense_symv_ms_median=median(sy), dense_symv_ms_min=min(sy),
+               dense_symv_GBps=8.0 * Nc * Nc / (median(sy) * 1e-3) / 1e9)
+    # (b) one cycle at degree 3 against its finest-level launches alone (the finest context still has Chebyshev(3): the mg is closed)
+    b, x, r = vec(N), vec(N), vec(N)
+
+    def finest_only():
+        fin.chebyshev_step_device(b.data_ptr(), x.data_ptr(), True)
+        fin.residual_device(b.data_ptr(), x.data_ptr(), r.data_ptr())
+        fin.chebyshev_step_device(b.data_ptr(), x.data_ptr(), False)
+    fin.setup_chebyshev("block_jacobi", degree=3, max_eigenvalue=est[-1])
+    fo = event_times_ms(torch, finest_only, reps)
+    mg = Multigrid(hier.contexts, hier.transfers)
+    cy = event_times_ms(torch, lambda: mg.vcycle_device(b.data_ptr(), x.data_ptr(), True), reps)
+    out.update(vcycle3_ms_median=median(cy), vcycle3_ms_min=min(cy), finest_level_only_ms_median=median(fo), finest_level_only_ms_min=min(fo),
+               coarser_levels_ms=median(cy) - median(fo), coarser_levels_over_finest_time=(median(cy) - median(fo)) / median(fo))
+    # (c) the solves
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=gen)
+    rhs = torch.empty(N, dtype=torch.float64, device="cuda")
+    fin.vmult_device(xs.data_ptr(), rhs.data_ptr())
+    out["solves"] = []
+    for m in (0, 2, 3, 5):
+        if mg is not None:
+            mg.close()
+            mg = None
+        if m:
+            for c, e in zip(hier.contexts[1:], est[1:]):
+                c.setup_chebyshev("block_jacobi", degree=m, max_eigenvalue=e)
+            mg = Multigrid(hier.contexts, hier.transfers)
+        else:
+            fin.setup_preconditioner("block_jacobi")
+        sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        si = fin.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+        wall = time.perf_counter() - w0
+        its = si["iterations"]
+        out["solves"].append({"preconditioner": "V-cycle, Chebyshev(%d) over block Jacobi, direct coarse solve" % m if m else "block Jacobi",
+                              "iterations": its, "products_with_finest_A": 1 + (its + 1) * 2 * m + its if m else 1 + its, "wall_s": wall,
+                              "ms_per_iteration": wall / max(its, 1) * 1e3, "residual": si["residual"],
+                              "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))})
+        print(json.dumps(out["solves"][-1]), flush=True)
+    bj = out["solves"][0]["wall_s"]
+    for srec in out["solves"]:
+        srec["wall_over_block_jacobi"] = srec["wall_s"] / bj
+    out["case_wall_s"] = time.time() - t0
+    hier.mg = mg
+    hier.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
@@ -254,11 +349,21 @@ def main():
     ap.add_argument("--no-solve", action="store_true", help="skip the full headline solve")
     ap.add_argument("--chebyshev", action="store_true", help="add the Chebyshev section (FE_DGQ(3) diag_first and FE_AggloDGP(3))")
     ap.add_argument("--transfer", action="store_true", help="the level-transfer section alone (default --out: profiles/r08_transfer.json)")
+    ap.add_argument("--vcycle", action="store_true", help="the V-cycle section alone (default --out: profiles/r09_vcycle.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.vcycle:
+        out = {"tool": "tools/solve_bench.py --vcycle", "version": pa.load_library().pdh_version().decode(),
+               "device": torch.cuda.get_device_name(0)}
+        out.update(vcycle_case(pa, torch, args.cells, args.reps))
+        doc = json.dumps(out, indent=1)
+        with open(args.out or os.path.join(ROOT, "profiles", "r09_vcycle.json"), "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     if args.transfer:
         out = {"tool": "tools/solve_bench.py --transfer", "version": pa.load_library().pdh_version().decode(),
                "device": torch.cuda.get_device_name(0), "pairs": []}
