@@ -11,7 +11,9 @@
 // matrix), after the case of the reference's test/polydeal/poisson.cc, whose printed line "L2 error:0.00647702" it reproduces.
 // `--chebyshev <degree>` after it preconditions that solve with the Chebyshev polynomial of that degree over block Jacobi
 // (pdh_setup_chebyshev: smoothing range 20, 20 CG steps for the eigenvalue estimate - the reference's multigrid smoother settings).
-// Usage: poisson [--device-solve [--chebyshev <degree>]] [path/to/t3.msh]
+// `--smoother-f32` after that lets the polynomial read a float32 copy of the matrix and of the block inverses
+// (pdh_set_smoother_precision); CG itself, every vector and every sum stay double.
+// Usage: poisson [--device-solve [--chebyshev <degree> [--smoother-f32]]] [path/to/t3.msh]
 #include "../polydeal_amd/csrc/host/polydeal_host.h"
 #include "host_solver.h"
 
@@ -39,6 +41,7 @@ int bench(int argc, char **argv); // device-resident timing (below)
 int reference_case();             // test/polydeal/poisson.cc, solved on the device (below)
 
 int chebyshev_degree = 0; // --chebyshev: 0 = plain block Jacobi
+bool smoother_f32 = false; // --smoother-f32: the Chebyshev polynomial reads the float32 shadow
 
 // preconditioned CG on the resident matrix: block Jacobi or Chebyshev over it, the stop rule of example_solver::solve_cg
 int device_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<double> &x)
@@ -47,7 +50,9 @@ int device_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<doubl
   const pdh_cg_control control = {20000, 1e-13, 0.0};
   pdh_cg_result res;
   const pdh_chebyshev_control cheb = {PDH_PREC_BLOCK_JACOBI, chebyshev_degree, 20.0, 20, 0.0};
-  const int rc = chebyshev_degree > 0 ? pdh_setup_chebyshev(ctx, &cheb, nullptr) : pdh_setup_preconditioner(ctx, PDH_PREC_BLOCK_JACOBI);
+  int rc = chebyshev_degree > 0 ? pdh_setup_chebyshev(ctx, &cheb, nullptr) : pdh_setup_preconditioner(ctx, PDH_PREC_BLOCK_JACOBI);
+  if (rc == PDH_OK && smoother_f32)
+    rc = pdh_set_smoother_precision(ctx, PDH_SMOOTHER_F32);
   if (rc != PDH_OK || pdh_solve_cg(ctx, &control, rhs.data(), x.data(), &res) != PDH_OK)
     {
       std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
@@ -76,10 +81,21 @@ int main(int argc, char **argv)
             }
           argc -= 2;
           argv += 2;
+          if (argc > 1 && std::strcmp(argv[1], "--smoother-f32") == 0)
+            {
+              smoother_f32 = true;
+              --argc;
+              ++argv;
+            }
         }
-      if (reference_case() != 0)
-        return 1;
     }
+  if (argc > 1 && std::strcmp(argv[1], "--smoother-f32") == 0)
+    {
+      std::fprintf(stderr, "--smoother-f32 is accepted only after --device-solve --chebyshev <degree>\n");
+      return 1;
+    }
+  if (on_device && reference_case() != 0)
+    return 1;
   constexpr int dim = 2;
   const std::string mesh = find_mesh(argc, argv);
   const double pi = M_PI;

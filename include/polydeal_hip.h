@@ -509,6 +509,37 @@ int  pdh_mg_create(int n_levels, pdh_ctx *const *levels /* coarse to fine */,
 void pdh_mg_destroy(pdh_mg *mg);
 int  pdh_mg_vcycle_device(pdh_mg *mg, const double *d_b, double *d_x, int zero_initial_guess);
 
+/* Single-precision smoother matrices (pdh_shadow.hip).  A preconditioner does not need double-precision matrix entries, and the product
+ * with the resident matrix is a pure read stream: pdh_set_smoother_precision(ctx, PDH_SMOOTHER_F32) builds a float32 copy - the SHADOW - of
+ * the values as they stand (rows in ascending column order, zero-padded to 8 bytes) and of the block inverses pdh_setup_chebyshev just
+ * built (rounded entry by entry: exactly symmetric still; the point-Jacobi inverse, one vector, stays double), on the device, without
+ * reading anything back.  While F32 is in force the shadow serves the Chebyshev application wherever it runs - pdh_chebyshev_step_device,
+ * PDH_PREC_CHEBYSHEV inside pdh_precondition_device and pdh_solve_cg*, the smoother of this level inside a V-cycle - and the residual of
+ * this level inside a V-cycle.  Every vector, every product ((double)a * x) and every sum stays double, in the fixed orders of the double
+ * kernels (no atomics: the same call on the same data gives the same bits), so the preconditioner is EXACTLY the Chebyshev polynomial /
+ * V-cycle of the rounded matrices, a fixed symmetric positive operator, and CG converges to double accuracy as before.  The double matrix
+ * keeps serving pdh_vmult*, pdh_residual_device, CG's own A p and b - A x, the eigenvalue estimate and the coarsest level's solver
+ * (PDH_PREC_DIRECT inverts the unrounded matrix).  Levels of one hierarchy may mix precisions.
+ *   Needs PDH_PREC_CHEBYSHEV set up and current on the context (else PDH_ESTATE; a context with PDH_PREC_MULTIGRID attached is PDH_ESTATE
+ * too: choose the precision of every level BEFORE pdh_mg_create); any other precision value is PDH_EINVAL.  It counts as a set-up call:
+ * a pdh_mg that already holds the context as a level turns stale (PDH_ESTATE naming the level).  It detaches nothing and does NOT repeat the
+ * eigenvalue estimate: lambda_lo, lambda_hi and the coefficients stay those of the double set-up - rounding perturbs every entry by at most
+ * 2^-24 = 6e-8 relative, and so the spectrum of P^-1 A by about as much, which the 1.2 safety factor of lambda_hi covers a million times
+ * over.  PDH_SMOOTHER_F64 switches back and keeps the buffers (grow-only).  Every pdh_setup_preconditioner, pdh_setup_chebyshev and
+ * pdh_setup_direct resets the precision to F64; once the values changed the staleness rules of the set-up apply (PDH_ESTATE).  Out of device
+ * memory: PDH_EDEVICE, F64 stays in force and the Chebyshev set-up valid.  The shadow takes half the bytes of the values (plus half those of
+ * the block inverses).
+ *   What it is for: levels whose diagonal blocks are well conditioned (cond_2 far below 2^24, as on block agglomerates).  The inverse of a
+ * block with cond_2 ~ 1e9 (FE_DGQ on the bounding box of a very irregular agglomerate) does not survive rounding to float32 - the call
+ * succeeds, the smoother it gives is a different and possibly indefinite operator.  Point Jacobi has no such limit.
+ *   pdh_smoother_precision: the one in force (< 0 on error).  pdh_smoother_vmult_device: y = A~ x, the product with the shadow on its own,
+ * with the rules of pdh_vmult_device; PDH_ESTATE unless F32 is in force and current.                                                      */
+#define PDH_SMOOTHER_F64 0
+#define PDH_SMOOTHER_F32 1
+int pdh_set_smoother_precision(pdh_ctx *ctx, int precision);
+int pdh_smoother_precision(pdh_ctx *ctx);
+int pdh_smoother_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

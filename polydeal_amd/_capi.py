@@ -20,6 +20,8 @@ PDH_OK = 0
 PDH_EINVAL, PDH_EUNSUPPORTED, PDH_EDEVICE, PDH_ESTATE, PDH_ENOCONV = -1, -2, -3, -4, -5
 PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI, PDH_PREC_CHEBYSHEV, PDH_PREC_DIRECT, PDH_PREC_MULTIGRID = 0, 1, 2, 3, 4, 5
 _PREC = {"none": PDH_PREC_NONE, "jacobi": PDH_PREC_JACOBI, "block_jacobi": PDH_PREC_BLOCK_JACOBI}
+PDH_SMOOTHER_F64, PDH_SMOOTHER_F32 = 0, 1
+_SMOOTHER = {"f64": PDH_SMOOTHER_F64, "f32": PDH_SMOOTHER_F32}
 CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
 
@@ -109,6 +111,7 @@ EXPORTS = [
     "pdh_transfer_destroy", "pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device",
     "pdh_restrict_and_add_device", "pdh_prolongate", "pdh_restrict",
     "pdh_setup_direct", "pdh_mg_create", "pdh_mg_destroy", "pdh_mg_vcycle_device",
+    "pdh_set_smoother_precision", "pdh_smoother_precision", "pdh_smoother_vmult_device",
 ]
 
 # (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
@@ -205,6 +208,9 @@ def _bind(lib):
     lib.pdh_mg_destroy.argtypes = [pdh_mg_p]
     lib.pdh_mg_destroy.restype = None
     lib.pdh_mg_vcycle_device.argtypes = [pdh_mg_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pdh_set_smoother_precision.argtypes = [pdh_ctx_p, C.c_int]
+    lib.pdh_smoother_precision.argtypes = [pdh_ctx_p]
+    lib.pdh_smoother_vmult_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
     return real
 
 
@@ -599,6 +605,24 @@ class Context:
         info = pdh_direct_info()
         self._chk(self.lib.pdh_setup_direct(self.h, C.byref(info)))
         return {"n_rows": int(info.n_rows), "pivot_min": float(info.pivot_min), "pivot_max": float(info.pivot_max)}
+
+    def set_smoother_precision(self, precision):
+        """'f32' | 'f64' (or PDH_SMOOTHER_*): with 'f32' the Chebyshev smoother set up last, and the residual of this level inside a
+        V-cycle, read a float32 copy of the matrix and of the block inverses built now from the values as they stand
+        (pdh_set_smoother_precision); vectors and sums stay double.  Every setup_* call goes back to 'f64'."""
+        self._chk(self.lib.pdh_set_smoother_precision(self.h, _SMOOTHER[precision] if isinstance(precision, str) else int(precision)))
+
+    @property
+    def smoother_precision(self):
+        """'f32' | 'f64': the one in force"""
+        rc = self.lib.pdh_smoother_precision(self.h)
+        if rc < 0:
+            self._chk(rc)
+        return {v: k for k, v in _SMOOTHER.items()}[rc]
+
+    def smoother_vmult_device(self, d_x, d_y):
+        """y = A~ x with the float32 copy of the matrix ('f32' in force); device pointers (ints), asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_smoother_vmult_device(self.h, C.c_void_p(d_x), C.c_void_p(d_y)))
 
     def chebyshev_step_device(self, d_b, d_x, zero_initial_guess=False):
         """One application of the smoother to b from the x in d_x (device pointers as ints); asynchronous on the context's stream."""

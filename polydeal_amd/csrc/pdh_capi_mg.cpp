@@ -169,7 +169,7 @@ int pdh_mg_cycle(pdh_mg *mg, const double *b, double *x, bool zero, const double
       pdh_mg::Level &L = mg->levels[(size_t)l];
       double *r = L.r.ptr<double>();
       PDH_TRY(pdh_cheb_apply(L.ctx, fin, A[(size_t)l], bl(l), xl(l), l < n - 1 || zero, nullptr, nullptr, st)); // pre-smoothing
-      PDH_HIP(fin, pdh_launch_vmult(&A[(size_t)l], xl(l), r, nullptr, st));                                       // r = b - A x
+      PDH_TRY(pdh_smoother_vmult(L.ctx, fin, A[(size_t)l], xl(l), r, st)); // r = b - A x, with the matrix the level's smoother reads
       PDH_HIP(fin, pdh_launch_residual_sub(L.n_rows, bl(l), r, st));
       PDH_HIP(fin, pdh_transfer_launch(mg->transfers[(size_t)l - 1], true, 0, r, mg->levels[(size_t)l - 1].b.ptr<double>(), st));
     }

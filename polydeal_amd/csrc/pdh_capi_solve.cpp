@@ -1,10 +1,12 @@
 // pdh_capi_solve.cpp — device driver of the C ABI, solving with the resident matrix (kernels: pdh_solve.hip): y = A x, the Jacobi /
 // block Jacobi inverses, CG, and the Chebyshev smoother / preconditioner.  The one CG recurrence (CgRun) serves the solver and the
 // eigenvalue estimate of the Chebyshev set-up; the host arithmetic of the latter is the planner's (pdh_plan.h).  The dense direct solve
-// (kernels: pdh_dense.hip) is one more preconditioner; the V-cycle (pdh_capi_mg.cpp) composes the helpers of this unit.
+// (kernels: pdh_dense.hip) is one more preconditioner; the V-cycle (pdh_capi_mg.cpp) composes the helpers of this unit.  The smoother may
+// read a float32 copy of the matrix and of the block inverses instead (pdh_set_smoother_precision; kernels: pdh_shadow.hip).
 #include "pdh_ctx.h"
 #include "pdh_dense.h"
 #include "pdh_launch.h"
+#include "pdh_shadow.h"
 
 #include <cmath>
 
@@ -109,6 +111,7 @@ static void new_setup(pdh_ctx *ctx)
   pdh_mg_detach(ctx);
   ctx->mg_gone = false;
   ++ctx->prec_epoch;
+  ctx->prob.sol.f32 = false; // the smoother precision belongs to one set-up (pdh_set_smoother_precision)
 }
 
 extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
@@ -179,14 +182,20 @@ int pdh_cheb_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const d
   const int m = (int)S.cheb_c2.size();
   if (!d || !r || !q || !dinv || m < 1)
     return fail(report, PDH_ESTATE, "the Chebyshev preconditioner is not set up");
+  // PDH_SMOOTHER_F32: the products read the shadow rows, the block branch of the update the float inverses (point Jacobi stays double)
+  const float *dinv32 = S.f32 && S.cheb_inner == PDH_PREC_BLOCK_JACOBI ? S.sh_dinv.ptr<float>() : nullptr;
   if (!zero)
-    PDH_HIP(report, pdh_launch_vmult(&A, x, q, nullptr, stream));
+    PDH_TRY(pdh_smoother_vmult(ctx, report, A, x, q, stream));
   for (int k = 0; k < m; ++k)
     {
       if (k > 0)
-        PDH_HIP(report, pdh_launch_vmult(&A, d, q, nullptr, stream));
-      PDH_HIP(report, pdh_launch_cheb_update(&A, k == 0, S.cheb_inner, dinv, b, (k == 0 && zero) ? nullptr : q, d, r, x, S.cheb_c1[k], S.cheb_c2[k],
-                                             k == 0 && zero, k == m - 1 ? rcg : nullptr, part, stream));
+        PDH_TRY(pdh_smoother_vmult(ctx, report, A, d, q, stream));
+      const double *qk = (k == 0 && zero) ? nullptr : q, *rcgk = k == m - 1 ? rcg : nullptr;
+      if (dinv32)
+        PDH_HIP(report, pdh_launch_cheb_update_f32(&A, k == 0, dinv32, b, qk, d, r, x, S.cheb_c1[k], S.cheb_c2[k], k == 0 && zero, rcgk, part, stream));
+      else
+        PDH_HIP(report, pdh_launch_cheb_update(&A, k == 0, S.cheb_inner, dinv, b, qk, d, r, x, S.cheb_c1[k], S.cheb_c2[k], k == 0 && zero, rcgk,
+                                               part, stream));
     }
   return PDH_OK;
 }
@@ -478,6 +487,101 @@ extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double
   PDH_TRY(prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   return cheb_apply(ctx, pdh_solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
+}
+
+// ---- single-precision smoother matrices (include/polydeal_hip.h: pdh_set_smoother_precision; kernels and layout: pdh_shadow.h) ---------
+int pdh_smoother_vmult(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *x, double *y, hipStream_t stream)
+{
+  const pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (!S.f32)
+    {
+      PDH_HIP(report, pdh_launch_vmult(&A, x, y, nullptr, stream));
+      return PDH_OK;
+    }
+  const PdhShadowArgs Sh{S.sh_values.ptr<float>(), S.sh_base.ptr<int64_t>()};
+  if (!Sh.values || !Sh.base)
+    return fail(report, PDH_ESTATE, "the single-precision smoother matrix is not set up");
+  PDH_HIP(report, pdh_launch_vmult_f32(&A, &Sh, x, y, stream));
+  return PDH_OK;
+}
+
+// the per-slot bases of the shadow rows, once per resident problem: they follow the row lengths, which a problem keeps
+static int shadow_bases(pdh_ctx *ctx)
+{
+  pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (S.sh_count > 0)
+    return PDH_OK;
+  const size_t n_owned = (size_t)ctx->prob.n_owned;
+  int64_t *d_base = S.sh_base.get<int64_t>(n_owned);
+  if (!d_base)
+    return fail(ctx, PDH_EDEVICE, "pdh_set_smoother_precision: out of device memory");
+  std::vector<int32_t> row_len(n_owned);
+  std::vector<int64_t> base(n_owned);
+  if (n_owned)
+    PDH_HIP(ctx, hipMemcpy(row_len.data(), ctx->prob.dev.row_len, n_owned * sizeof(int32_t), hipMemcpyDeviceToHost));
+  int64_t count = 0;
+  for (size_t s = 0; s < n_owned; ++s)
+    {
+      base[s] = count;
+      count += (int64_t)ctx->prob.dev.n * pdh_shadow_stride(row_len[s]);
+    }
+  if (n_owned)
+    PDH_HIP(ctx, hipMemcpy(d_base, base.data(), n_owned * sizeof(int64_t), hipMemcpyHostToDevice));
+  S.sh_count = std::max<int64_t>(count, 1);
+  return PDH_OK;
+}
+
+extern "C" int pdh_set_smoother_precision(pdh_ctx *ctx, int precision)
+{
+  PDH_TRY(need_problem(ctx, "pdh_set_smoother_precision"));
+  if (precision != PDH_SMOOTHER_F64 && precision != PDH_SMOOTHER_F32)
+    return fail(ctx, PDH_EINVAL, "pdh_set_smoother_precision: precision must be PDH_SMOOTHER_F64 or PDH_SMOOTHER_F32");
+  if (ctx->prec_kind == PDH_PREC_MULTIGRID)
+    return fail(ctx, PDH_ESTATE, "pdh_set_smoother_precision: the context has a multigrid preconditioner attached; choose the precision of "
+                                 "every level before pdh_mg_create");
+  if (ctx->prec_kind != PDH_PREC_CHEBYSHEV || ctx->mg_gone)
+    return fail(ctx, PDH_ESTATE, "pdh_set_smoother_precision: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
+  PDH_TRY(prec_checks(ctx));
+  pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (precision == PDH_SMOOTHER_F64)
+    {
+      S.f32 = false; // (the buffers stay, grow-only like the others)
+      ++ctx->prec_epoch;
+      return PDH_OK;
+    }
+  PDH_TRY(pdh_row_fits_lds(ctx));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  PDH_TRY(shadow_bases(ctx));
+  const bool block = S.cheb_inner == PDH_PREC_BLOCK_JACOBI;
+  const int64_t n = ctx->prob.dev.n, n_inv = block ? ctx->prob.n_owned * n * n : 0;
+  float *values = S.sh_values.get<float>((size_t)S.sh_count);
+  float *dinv32 = block ? S.sh_dinv.get<float>((size_t)n_inv) : nullptr;
+  if (!values || (block && !dinv32))
+    return fail(ctx, PDH_EDEVICE, "pdh_set_smoother_precision: out of device memory"); // (F64 stays in force, the set-up valid)
+  const PdhSolveArgs A = pdh_solve_args(ctx);
+  PDH_HIP(ctx, pdh_launch_shadow_rows(&A, S.sh_base.ptr<int64_t>(), values, ctx->stream));
+  if (block)
+    PDH_HIP(ctx, pdh_launch_shadow_round(S.dinv.ptr<double>(), dinv32, n_inv, ctx->stream));
+  S.f32 = true;
+  ++ctx->prec_epoch;
+  return PDH_OK;
+}
+
+extern "C" int pdh_smoother_precision(pdh_ctx *ctx)
+{
+  PDH_TRY(need_problem(ctx, "pdh_smoother_precision"));
+  return ctx->prob.sol.f32 ? PDH_SMOOTHER_F32 : PDH_SMOOTHER_F64;
+}
+
+extern "C" int pdh_smoother_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y)
+{
+  PDH_TRY(vmult_checks(ctx, d_x, d_y));
+  if (!ctx->prob.sol.f32)
+    return fail(ctx, PDH_ESTATE, "pdh_smoother_vmult_device: PDH_SMOOTHER_F32 is not in force (pdh_set_smoother_precision)");
+  if (ctx->prec_gen != ctx->values_gen)
+    return fail(ctx, PDH_ESTATE, "the values changed since pdh_set_smoother_precision: set the smoother up again");
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  return pdh_smoother_vmult(ctx, ctx, pdh_solve_args(ctx), d_x, d_y, ctx->stream);
 }
 
 // ---- dense direct solve (include/polydeal_hip.h: pdh_setup_direct; steps and layout: pdh_dense.h) ---------------------------------------

@@ -181,6 +181,11 @@ struct pdh_ctx
       // apply
       DevBuf dense_g, dense_tmp;
       int dense_ld = 0, dense_n = 0;
+      // pdh_set_smoother_precision (pdh_shadow.h): the float32 rows, their per-slot bases (they follow the pattern: computed once per
+      // problem) and the float32 block inverses, grow-only; f32: the smoother and the V-cycle residual of this context read them
+      DevBuf sh_values, sh_base, sh_dinv;
+      int64_t sh_count = 0; // entries of sh_values once sh_base is filled, 0 before
+      bool f32 = false;
     } sol;
   } prob;
 
@@ -350,6 +355,8 @@ int pdh_row_fits_lds(pdh_ctx *ctx); // PDH_EUNSUPPORTED on `ctx`: a row of more 
 // rcg / part: see pdh_launch_cheb_update.  Errors are reported on `report`.
 int pdh_cheb_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part,
                    hipStream_t stream);
+// y = A x as the smoother of `ctx` sees A: the float32 shadow while PDH_SMOOTHER_F32 is in force, else pdh_launch_vmult
+int pdh_smoother_vmult(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *x, double *y, hipStream_t stream);
 // z = P^-1 r with the preconditioner of `ctx` as set up - any kind but PDH_PREC_MULTIGRID, r and z disjoint - without the state checks
 int pdh_prec_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *r, double *z, const double *rcg, double *part,
                    hipStream_t stream);

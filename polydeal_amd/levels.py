@@ -122,18 +122,23 @@ class MultigridHierarchy:
         self.contexts = []
 
 
-def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = None, diag_first=True, degree=3, inner=None, device=0):
+def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = None, diag_first=True, degree=3, inner=None, device=0,
+                        smoother_precision="f64"):
     """The reference's agglomerated multigrid (examples/simplex_agglomerated_multigrid.cc:378-515) on one device: one context per level
     handler of `levels` (coarse to fine, e.g. block_hierarchy's), each assembled like assemble_levels does (the Cartesian description
     where it is taken); Chebyshev of `degree` over `inner` ('block_jacobi' up to 64 dofs per polytope, 'jacobi' above, unless given) as
     the smoother of every level above the coarsest, the dense direct solve on the coarsest (at most 1024 rows), the level transfers
-    and the V-cycle, which becomes the preconditioner of the finest context.  Returns a MultigridHierarchy; close() it."""
+    and the V-cycle, which becomes the preconditioner of the finest context.  smoother_precision 'f32': every level above the coarsest
+    smooths, and forms its residual, with a float32 copy of its matrix (Context.set_smoother_precision); CG and all vectors stay double.
+    Returns a MultigridHierarchy; close() it."""
     from ._capi import Context, Multigrid, PdhError
     from .handler import HostError
 
     variant = variant or SipVariant.assemble_dg_matrix()
     if inner is None:
         inner = "block_jacobi" if fe.n_dofs_per_cell <= 64 else "jacobi"
+    if smoother_precision not in ("f64", "f32"):
+        raise ValueError("smoother_precision must be 'f64' or 'f32'")
     contexts, transfers, info, mg = [], [], [], None
     try:
         for l, ah in enumerate(levels):
@@ -153,6 +158,8 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
                 ctx.set_problem(flat)
             ctx.assemble_device()
             info.append(ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree))
+            if l > 0 and smoother_precision == "f32":
+                ctx.set_smoother_precision("f32")
             if l > 0:
                 transfers.append(level_transfer(ctx, levels[l - 1], ah))
         mg = Multigrid(contexts, transfers)

@@ -21,7 +21,7 @@ CSRC = os.path.join("polydeal_amd", "csrc")
 # (name, source, extra flags) of every device unit.  This list must match the .hip units of polydeal_amd/csrc/Makefile (pdh_inst.hip once per
 # PDH_GROUP): a unit that is missing here is a unit whose kernels the comparison does not see.
 UNITS = [("inst_g%d" % g, "pdh_inst.hip", ["-DPDH_GROUP=%d" % g]) for g in range(8)] + [
-    (u, "pdh_%s.hip" % u, []) for u in ("rhs", "eval", "exchange", "moment", "terms", "cartgen", "tiled", "solve", "transfer")]
+    (u, "pdh_%s.hip" % u, []) for u in ("rhs", "eval", "exchange", "moment", "terms", "cartgen", "tiled", "solve", "shadow", "transfer")]
 
 
 def makefile_flags(csrc):
@@ -33,6 +33,8 @@ def makefile_flags(csrc):
 
 def compile_unit(csrc, out_dir, unit):
     name, src, defs = unit
+    if not os.path.exists(os.path.join(csrc, src)):  # a unit the other side does not have yet
+        return name, None
     out = os.path.join(out_dir, name + ".s")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     subprocess.run([hipcc] + makefile_flags(csrc) + defs + ["--cuda-device-only", "-S", src, "-o", out], cwd=csrc, check=True,
@@ -84,6 +86,10 @@ def main():
             asm = {side: dict(j.result() for j in js) for side, js in jobs.items()}
         bad = 0
         for name, _, _ in UNITS:
+            if asm["rev"][name] is None or asm["tree"][name] is None:
+                print("%-9s %s" % (name, "not at %s: a new unit" % a.rev if asm["rev"][name] is None else "not in the tree: DIFFERENT"))
+                bad += asm["tree"][name] is None
+                continue
             fa, fb = functions(asm["rev"][name]), functions(asm["tree"][name])
             diff = (["only at %s: %s" % (a.rev, s) for s in sorted(set(fa) - set(fb))] + ["only in the tree: %s" % s for s in sorted(set(fb) - set(fa))] +
                     ["differs: %s" % s for s in sorted(set(fa) & set(fb)) if fa[s] != fb[s]])

@@ -28,6 +28,14 @@ coarsest level (wall time, it synchronises) and k_dense_symv alone (HIP events);
 launches restricted to the finest level (pre-smoothing from zero, residual, post-smoothing), both by HIP events in the same process -
 their difference is what the coarser levels cost; (c) the solve b = A x*, rel_tol 1e-13, with block Jacobi and with the V-cycle at
 smoother degrees 2, 3 and 5: iterations, products with the finest A, seconds.  No condition is checked: the table is the result.
+
+Single-precision smoother section (--vcycle --smoother-f32, or --chebyshev --smoother-f32, alone; pdh_set_smoother_precision), written to
+profiles/r10_smoother_f32.json unless --out says otherwise (the --chebyshev form writes only where --out says).  Everything in ONE process,
+the F64 path measured there being the yardstick: k_vmult against k_vmult_f32 on the finest matrix, alternating, in ms and in TB/s of the
+bytes each must move (values, the gathered x, the index arrays, y); the shadow's bytes and its set-up time next to the block-inverse
+set-up; one V-cycle with either precision; and the solve b = A x*, rel_tol 1e-13, F64 and F32 alternating, twice each.  Two conditions
+(fields f32_solve_faster_beyond_spread, f32_vmult_faster_beyond_spread): the F32 solve and the F32 product are faster than the F64 ones by
+more than the spread between the two F64 repeats.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -342,6 +350,143 @@ def vcycle_case(pa, torch, cells, reps):
     return out
 
 
+def vmult_bytes(st, n, N, f32):
+    """what one product must move: the values, the x gathered per slot (row_len doubles), blk_dof per block and the per-slot arrays
+    (row_base, row_len, diag_L, own_row, blk_ptr; the shadow adds its base), and y"""
+    nv, slots = st["n_values"], st["n_owned_agg"]
+    per_slot = 8 + 4 + 4 + 4 + 8 + (8 if f32 else 0)
+    return (4.0 if f32 else 8.0) * nv + 8.0 * nv / n + 4.0 * nv / (n * n) + per_slot * slots + 8.0 * N
+
+
+def smoother_f32_case(pa, torch, cells, reps, vcycle):
+    """the single-precision smoother figures: see the module docstring"""
+    from polydeal_amd._capi import Multigrid
+    from polydeal_amd.levels import block_hierarchy, multigrid_hierarchy
+
+    t0 = time.time()
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    fe = pa.FE_DGQ(3, 3)
+    n = fe.n_dofs_per_cell
+    degree = 3 if vcycle else 5
+    stream = torch.cuda.current_stream().cuda_stream
+    if vcycle:  # the hierarchy of the V-cycle section
+        handlers = block_hierarchy(grid, fe, [b for b in (32, 16, 8, 4, 2) if 2 * b <= cells])
+        hier = multigrid_hierarchy(handlers, fe, pa.SipVariant.poisson_example(fe), diag_first=True, degree=degree)
+        contexts, transfers, info, first_mg = hier.contexts, hier.transfers, hier.info, hier.mg
+        hier.mg = None
+        N = handlers[-1].n_dofs
+    else:  # the headline level alone, Chebyshev(5) over block Jacobi as its preconditioner
+        ah, _ = handler(pa, cells, "dgq")
+        ctx = pa.Context(0)
+        ctx.set_problem(ah.flatten(pa.SipVariant.poisson_example(fe), True, False))
+        ctx.assemble_device()
+        contexts, transfers, info, first_mg = [ctx], [], [ctx.setup_chebyshev("block_jacobi", degree=degree)], None
+        N = ah.n_dofs
+    for c in contexts:
+        c.set_stream(stream)
+    fin = contexts[-1]
+    est = [i.get("estimate") for i in info]
+    stats = [c.stats() for c in contexts]
+    out = {"element": "FE_DGQ(3)", "cells_per_axis": cells, "preconditioner": "V-cycle" if vcycle else "Chebyshev", "smoother_degree": degree,
+           "rows": [c.n_rows for c in contexts], "n_values_finest": stats[-1]["n_values"]}
+    smooth = list(range(1, len(contexts))) if vcycle else [0]
+    state = {"mg": first_mg}
+
+    def remake(prec):
+        """every smoother level set up again with its own estimate (F64), then `prec`; the V-cycle attached again"""
+        if state["mg"] is not None:
+            state["mg"].close()
+            state["mg"] = None
+        for l in smooth:
+            contexts[l].setup_chebyshev("block_jacobi", degree=degree, max_eigenvalue=est[l])
+            if prec == "f32":
+                contexts[l].set_smoother_precision("f32")
+        if vcycle:
+            state["mg"] = Multigrid(contexts, transfers)
+    try:
+        # the shadow: bytes and set-up time (the first call allocates; the later ones convert only), next to the block-inverse set-up
+        if state["mg"] is not None:
+            state["mg"].close()
+            state["mg"] = None
+        inv = event_times_ms(torch, lambda: fin.setup_preconditioner("block_jacobi"), reps)
+        fin.setup_chebyshev("block_jacobi", degree=degree, max_eigenvalue=est[-1])
+        t = []
+        for _ in range(reps + 1):
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            fin.set_smoother_precision("f32")
+            torch.cuda.synchronize()
+            t.append((time.perf_counter() - w0) * 1e3)
+        sh_rows = [4.0 * st["n_values"] for st in stats]  # (n = 64: every row length is even, no pad entries)
+        sh_inv = [4.0 * st["n_owned_agg"] * n * n for st in stats]
+        lv = smooth
+        out.update(shadow_rows_bytes_finest=sh_rows[-1], shadow_inverse_bytes_finest=sh_inv[-1],
+                   shadow_bytes_all_smoother_levels=sum(sh_rows[l] + sh_inv[l] for l in lv),
+                   shadow_setup_first_wall_ms=t[0], shadow_setup_wall_ms_median=median(t[1:]), shadow_setup_wall_ms_min=min(t[1:]),
+                   shadow_setup_GBps=(12.0 * stats[-1]["n_values"] + 12.0 * stats[-1]["n_owned_agg"] * n * n) / (median(t[1:]) * 1e-3) / 1e9,
+                   block_inverse_setup_ms_median=median(inv))
+        # the two products, alternating (F32 is in force on the finest context; pdh_vmult_device keeps reading the doubles)
+        x = torch.rand(N, dtype=torch.float64, device="cuda")
+        y = torch.empty(N, dtype=torch.float64, device="cuda")
+        f64 = lambda: fin.vmult_device(x.data_ptr(), y.data_ptr())
+        f32 = lambda: fin.smoother_vmult_device(x.data_ptr(), y.data_ptr())
+        vm = {"f64": [], "f32": []}
+        for _ in range(2):
+            vm["f64"].append(event_times_ms(torch, f64, reps))
+            vm["f32"].append(event_times_ms(torch, f32, reps))
+        b64, b32 = vmult_bytes(stats[-1], n, N, False), vmult_bytes(stats[-1], n, N, True)
+        m64, m32 = [median(v) for v in vm["f64"]], [median(v) for v in vm["f32"]]
+        spread = abs(m64[0] - m64[1])
+        out.update(vmult_ms_medians=m64, vmult_f32_ms_medians=m32, vmult_ms_min=min(map(min, vm["f64"])), vmult_f32_ms_min=min(map(min, vm["f32"])),
+                   vmult_bytes=b64, vmult_f32_bytes=b32, vmult_TBps=b64 / (median(m64) * 1e-3) / 1e12,
+                   vmult_f32_TBps=b32 / (median(m32) * 1e-3) / 1e12, vmult_spread_ms=spread, vmult_f32_speedup=median(m64) / median(m32),
+                   f32_vmult_faster_beyond_spread=bool(min(m64) - max(m32) > spread))
+        print(json.dumps({k: out[k] for k in ("vmult_ms_medians", "vmult_f32_ms_medians", "vmult_TBps", "vmult_f32_TBps")}), flush=True)
+        # one application of the preconditioner with either precision
+        r, z = torch.rand(N, dtype=torch.float64, device="cuda"), torch.empty(N, dtype=torch.float64, device="cuda")
+        for prec in ("f64", "f32"):
+            remake(prec)
+            ap = event_times_ms(torch, lambda: fin.precondition_device(r.data_ptr(), z.data_ptr()), reps)
+            out["application_%s_ms_median" % prec], out["application_%s_ms_min" % prec] = median(ap), min(ap)
+        # the solves, alternating
+        gen = torch.Generator(device="cuda").manual_seed(1)
+        xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=gen)
+        rhs = torch.empty(N, dtype=torch.float64, device="cuda")
+        fin.vmult_device(xs.data_ptr(), rhs.data_ptr())
+        out["solves"] = []
+        per_it = 2 * degree if vcycle else degree - 1  # products of one application with the smoother's matrix
+        for prec in ("f64", "f32", "f64", "f32"):
+            remake(prec)
+            sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            si = fin.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+            wall = time.perf_counter() - w0
+            its = si["iterations"]
+            res = torch.empty(N, dtype=torch.float64, device="cuda")
+            fin.residual_device(rhs.data_ptr(), sol.data_ptr(), res.data_ptr())
+            out["solves"].append({"smoother_precision": prec, "iterations": its, "products_with_A_double": 1 + its,
+                                  "products_with_the_smoother_matrix": (its + 1) * per_it, "wall_s": wall,
+                                  "ms_per_iteration": wall / max(its, 1) * 1e3, "residual": si["residual"],
+                                  "true_relative_residual": float(torch.linalg.norm(res) / torch.linalg.norm(rhs)),
+                                  "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))})
+            print(json.dumps(out["solves"][-1]), flush=True)
+        w64 = [s_["wall_s"] for s_ in out["solves"] if s_["smoother_precision"] == "f64"]
+        w32 = [s_["wall_s"] for s_ in out["solves"] if s_["smoother_precision"] == "f32"]
+        out.update(solve_f64_wall_s=w64, solve_f32_wall_s=w32, solve_f64_spread_s=abs(w64[0] - w64[1]),
+                   solve_f32_speedup=median(w64) / median(w32),
+                   f32_solve_faster_beyond_spread=bool(min(w64) - max(w32) > abs(w64[0] - w64[1])))
+    finally:
+        if state["mg"] is not None:
+            state["mg"].close()
+        for t_ in transfers:
+            t_.close()
+        for c in contexts:
+            c.close()
+    out["case_wall_s"] = time.time() - t0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
@@ -350,11 +495,26 @@ def main():
     ap.add_argument("--chebyshev", action="store_true", help="add the Chebyshev section (FE_DGQ(3) diag_first and FE_AggloDGP(3))")
     ap.add_argument("--transfer", action="store_true", help="the level-transfer section alone (default --out: profiles/r08_transfer.json)")
     ap.add_argument("--vcycle", action="store_true", help="the V-cycle section alone (default --out: profiles/r09_vcycle.json)")
+    ap.add_argument("--smoother-f32", action="store_true",
+                    help="with --vcycle or --chebyshev: the single-precision smoother section alone (--vcycle: default --out profiles/r10_smoother_f32.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.smoother_f32:
+        if not (args.vcycle or args.chebyshev):
+            ap.error("--smoother-f32 goes with --vcycle or --chebyshev")
+        out = {"tool": "tools/solve_bench.py --%s --smoother-f32" % ("vcycle" if args.vcycle else "chebyshev"),
+               "version": pa.load_library().pdh_version().decode(), "device": torch.cuda.get_device_name(0)}
+        out.update(smoother_f32_case(pa, torch, args.cells, args.reps, args.vcycle))
+        doc = json.dumps(out, indent=1)
+        path = args.out or (os.path.join(ROOT, "profiles", "r10_smoother_f32.json") if args.vcycle else None)
+        if path:
+            with open(path, "w") as f:
+                f.write(doc + "\n")
+        print(doc)
+        return
     if args.vcycle:
         out = {"tool": "tools/solve_bench.py --vcycle", "version": pa.load_library().pdh_version().decode(),
                "device": torch.cuda.get_device_name(0)}
