@@ -462,6 +462,52 @@ int pdh_restrict_and_add_device  (pdh_transfer *t, const double *d_fine,   doubl
 int pdh_prolongate(pdh_transfer *t, const double *coarse, double *fine);
 int pdh_restrict  (pdh_transfer *t, const double *fine,   double *coarse);
 
+/* Coarse level matrix as the Galerkin product A_c = P^T A_f P (pdh_galerkin.hip): the reference's AmgProjector::compute_level_matrices
+ * (include/multigrid_amg.h:267-305) over the injection of the transfer, without the injection matrix.  With par() the parent map and B_X
+ * the Kronecker injection block of fine polytope X,
+ *   A_c[C, C'] = sum over the fine blocks (F, F') with par(F) = C, par(F') = C' of  B_F^T A_f[F, F'] B_F'.
+ * If fine polytopes share a face their parents are equal or share a face, so on nested levels every fine block lands in ONE block of the
+ * coarse level's own face-neighbour pattern: the product is written into the rows the coarse context already has, and everything that
+ * reads them (pdh_vmult*, every pdh_setup_*, pdh_copy_values) works as after pdh_assemble_device.  At most 64 dofs per polytope.
+ *
+ * pdh_galerkin_plan, host-only: which fine blocks every coarse block receives, and in which order they are added.  A level is given by
+ * the block lists of its resident rows - slot s is the s-th polytope, blk_dof[blk_ptr[s] + t] the first global dof of the t-th block of
+ * its rows in value order (ascending col_offset or dof_offset, whichever orders the pattern) - and what the refusals read.  Output: a
+ * CSR over the coarse blocks, block b = coarse->blk_ptr[slot] + t; plan_ptr [coarse->blk_ptr[n] + 1], plan_slot / plan_pos
+ * [fine->blk_ptr[n]]: fine slot and block position of every entry, ascending (slot, position) inside a coarse block - the summation
+ * order.  Runs pdh_check_transfer first.  PDH_EINVAL: a level's slot count, row count or dof offsets differ from the transfer's; a block
+ * dof that is not the first dof of a polytope; a fine block whose pair of parents is no block of the coarse pattern (levels not nested,
+ * or patterns that are not face-neighbour patterns); a coarse block that receives nothing.  PDH_EUNSUPPORTED: more than 64 dofs per
+ * polytope (3-D FE_DGQ(4..7), which the transfers themselves accept); a level that does not own all its rows or was set in
+ * PDH_EXCHANGE_GHOST mode; levels on different devices.  pdh_last_error(NULL) says which.                                        */
+typedef struct pdh_galerkin_level
+{
+  int32_t n_slots;             /* owned polytopes                                                     */
+  int32_t n_rows_owned, n_rows;/* rows of the owned polytopes, rows of the level                      */
+  int32_t exchange_mode;       /* PDH_EXCHANGE_* the problem was set in                               */
+  int32_t device;
+  const int64_t *blk_ptr;      /* [n_slots + 1]                                                       */
+  const int32_t *blk_dof;      /* [blk_ptr[n_slots]]                                                  */
+  const int32_t *dof_offset;   /* [n_slots] first dof of every slot's polytope                        */
+} pdh_galerkin_level;
+int pdh_galerkin_plan(const pdh_transfer_desc *d, const pdh_galerkin_level *fine, const pdh_galerkin_level *coarse, int64_t *plan_ptr,
+                      int32_t *plan_slot, int32_t *plan_pos);
+/* Host-only: the 1-D matrices the product applies, out [n_fine][dim][p+1][p+1]: those of pdh_transfer_matrices_1d with every row that lies
+ * within 64 ulp of a unit vector made that unit vector.  Such a row belongs to a fine support point that IS a coarse one (the corners and
+ * faces of nested boxes), where the injection is exactly 0 and 1; the rounded Horner form leaves 1e-19 .. 1e-17 in the zeros, which is
+ * nothing to a transfer but the whole of an entry of P^T A P that is structurally zero.  The factors of the product and of pdh_prolongate* / pdh_restrict* thus differ
+ * by those 1e-19 .. 1e-17 (64 ulp at the very most), inside the 1e-13 of the sum of absolute products every row of either is held to. */
+int pdh_galerkin_matrices_1d(const pdh_transfer_desc *d, double *out);
+/* coarse's values = P^T A_f P, A_f the values of the context `t` was created on as they stand.  PDH_ESTATE: that context has no resident
+ * problem or its values were never assembled (pdh_assemble*, or a pdh_galerkin_device into it), or `coarse` has no resident problem -
+ * `coarse` needs its pattern only, its values are overwritten.  The refusals of pdh_galerkin_plan apply.  The plan is built at the first
+ * call and kept on the transfer until a pdh_set_problem* on either context.  One kernel on the fine context's stream, one wave per coarse
+ * block, every sum in a fixed order and no atomics: the same call on the same data gives the same bits.  A set-up call: it synchronises
+ * both streams before it starts and the fine one before it returns.  Afterwards `coarse`'s values count as assembled and CHANGED - a
+ * preconditioner set up before and a pdh_mg that holds `coarse` turn stale as after pdh_assemble_device, which may also overwrite them
+ * again later.  A later change of the fine values does not refresh the coarse ones.  Errors are reported on the fine context.        */
+int pdh_galerkin_device(pdh_transfer *t, pdh_ctx *coarse);
+
 /* Dense direct solve on the resident matrix (pdh_dense.hip): the coarse solver of a multigrid hierarchy, the reference's MGCoarseDirect
  * (examples/simplex_agglomerated_multigrid.cc:71-100, used at :476).  For a context that owns all rows with PDH_EXCHANGE_NONE (else PDH_EUNSUPPORTED,
  * like pdh_setup_chebyshev) and has at most 1024 rows (more: PDH_EUNSUPPORTED; 1024 rows are 16 polytopes of 64 dofs).  The set-up runs on

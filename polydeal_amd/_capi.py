@@ -80,6 +80,11 @@ class pdh_transfer_desc(C.Structure):
                 ("coarse_dof_offset", C.c_void_p), ("parent", C.c_void_p)]
 
 
+class pdh_galerkin_level(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("n_rows_owned", C.c_int32), ("n_rows", C.c_int32), ("exchange_mode", C.c_int32),
+                ("device", C.c_int32), ("blk_ptr", C.c_void_p), ("blk_dof", C.c_void_p), ("dof_offset", C.c_void_p)]
+
+
 class pdh_problem(C.Structure):
     _fields_ = [
         ("dim", C.c_int32), ("degree", C.c_int32), ("basis", C.c_int32), ("n_agg", C.c_int32),
@@ -112,6 +117,7 @@ EXPORTS = [
     "pdh_restrict_and_add_device", "pdh_prolongate", "pdh_restrict",
     "pdh_setup_direct", "pdh_mg_create", "pdh_mg_destroy", "pdh_mg_vcycle_device",
     "pdh_set_smoother_precision", "pdh_smoother_precision", "pdh_smoother_vmult_device",
+    "pdh_galerkin_plan", "pdh_galerkin_device",
 ]
 
 # (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
@@ -211,6 +217,9 @@ def _bind(lib):
     lib.pdh_set_smoother_precision.argtypes = [pdh_ctx_p, C.c_int]
     lib.pdh_smoother_precision.argtypes = [pdh_ctx_p]
     lib.pdh_smoother_vmult_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
+    lib.pdh_galerkin_plan.argtypes = [P(pdh_transfer_desc), P(pdh_galerkin_level), P(pdh_galerkin_level), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pdh_galerkin_device.argtypes = [pdh_transfer_p, pdh_ctx_p]
+    lib.pdh_galerkin_matrices_1d.argtypes = [P(pdh_transfer_desc), C.c_void_p]
     return real
 
 
@@ -324,11 +333,45 @@ class TransferDesc:
         self._chk(load_library().pdh_transfer_matrices_1d(C.byref(self.c), out.ctypes.data))
         return out
 
+    def galerkin_matrices_1d(self):
+        """[n_fine][dim][p+1][p+1]: the 1-D factors pdh_galerkin_device applies - matrices_1d() with the rows of fine support points that
+        are coarse ones made exact unit vectors (host only)."""
+        out = np.empty((self.n_fine, self.dim, self.degree + 1, self.degree + 1))
+        self._chk(load_library().pdh_galerkin_matrices_1d(C.byref(self.c), out.ctypes.data))
+        return out
+
     def children(self):
         """(child_ptr [n_coarse+1], child_idx [n_fine]): the summation order of the restriction (host only)."""
         ptr, idx = np.empty(self.n_coarse + 1, dtype=np.int32), np.empty(self.n_fine, dtype=np.int32)
         self._chk(load_library().pdh_transfer_children(C.byref(self.c), ptr.ctypes.data, idx.ctypes.data))
         return ptr, idx
+
+
+class GalerkinLevel:
+    """Owns the NumPy arrays behind a pdh_galerkin_level: the block lists of one level's resident rows (slot s = polytope s; blk_dof
+    [blk_ptr[s] + t] = first global dof of the t-th block of its rows in value order) and what the refusals of galerkin_plan read."""
+
+    def __init__(self, *, blk_ptr, blk_dof, dof_offset, n_rows, n_rows_owned=None, exchange_mode=0, device=0):
+        self.blk_ptr = np.ascontiguousarray(blk_ptr, dtype=np.int64)
+        self.blk_dof = np.ascontiguousarray(blk_dof, dtype=np.int32)
+        self.dof_offset = np.ascontiguousarray(dof_offset, dtype=np.int32)
+        if self.blk_ptr.shape != (len(self.dof_offset) + 1,) or self.blk_dof.shape != (int(self.blk_ptr[-1]),):
+            raise ValueError("blk_ptr [n_slots + 1], blk_dof [blk_ptr[-1]], dof_offset [n_slots]")
+        self.c = pdh_galerkin_level(len(self.dof_offset), int(n_rows if n_rows_owned is None else n_rows_owned), int(n_rows),
+                                    int(exchange_mode), int(device), self.blk_ptr.ctypes.data, self.blk_dof.ctypes.data,
+                                    self.dof_offset.ctypes.data)
+
+
+def galerkin_plan(desc: TransferDesc, fine: GalerkinLevel, coarse: GalerkinLevel):
+    """pdh_galerkin_plan (host only, no GPU): (plan_ptr [n coarse blocks + 1], plan_slot, plan_pos [n fine blocks]) - the fine blocks
+    (slot, block position) every coarse block of P^T A P receives, in summation order."""
+    lib = load_library()
+    ptr = np.empty(int(coarse.blk_ptr[-1]) + 1, dtype=np.int64)
+    slot, pos = np.empty(int(fine.blk_ptr[-1]), dtype=np.int32), np.empty(int(fine.blk_ptr[-1]), dtype=np.int32)
+    rc = lib.pdh_galerkin_plan(C.byref(desc.c), C.byref(fine.c), C.byref(coarse.c), ptr.ctypes.data, slot.ctypes.data, pos.ctypes.data)
+    if rc != PDH_OK:
+        raise PdhError(rc, lib.pdh_last_error(None).decode())
+    return ptr, slot, pos
 
 
 class Transfer:
@@ -359,6 +402,12 @@ class Transfer:
     def restrict_and_add_device(self, d_fine, d_coarse):
         """coarse += P^T fine"""
         self._dev(self.lib.pdh_restrict_and_add_device, d_fine, d_coarse)
+
+    def galerkin_device(self, coarse_ctx):
+        """The values of `coarse_ctx` (a Context with its problem resident: the pattern is all it needs) become P^T A P, A the values of
+        this transfer's context as they stand (pdh_galerkin_device).  Synchronises; a preconditioner of `coarse_ctx` set up before is
+        stale afterwards."""
+        self.ctx._chk(self.lib.pdh_galerkin_device(self.h, coarse_ctx.h))
 
     def _host(self, fn, src, n_src, n_dst):
         a = np.ascontiguousarray(src, dtype=np.float64)

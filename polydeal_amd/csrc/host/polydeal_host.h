@@ -1873,6 +1873,8 @@ public:
   {
     check(pdh_restrict_and_add_device(t, d_src, d_dst), "pdh_restrict_and_add_device");
   }
+  // the values of `coarse` become P^T A P, A the values of this transfer's context as they stand (pdh_galerkin_device)
+  void galerkin_device(pdh_ctx *coarse) const { check(pdh_galerkin_device(t, coarse), "pdh_galerkin_device"); }
 
 private:
   static void need(bool ok, const char *msg)
@@ -1889,5 +1891,16 @@ private:
   pdh_transfer *t = nullptr;
   size_t n_fine, n_coarse;
 };
+
+// AmgProjector::compute_level_matrices (reference include/multigrid_amg.h:267-305): matrix[l] = P_l^T matrix[l+1] P_l on the device,
+// fine to coarse.  contexts: coarse to fine, every one with its problem resident, the finest assembled; transfers[l] connects level l
+// and l + 1 and lives on contexts[l + 1].
+inline void compute_level_matrices(const std::vector<pdh_ctx *> &contexts, const std::vector<const MGTransferAgglomeration *> &transfers)
+{
+  if (contexts.size() != transfers.size() + 1)
+    throw std::invalid_argument("compute_level_matrices: one transfer per pair of levels");
+  for (size_t l = transfers.size(); l > 0; --l)
+    transfers[l - 1]->galerkin_device(contexts[l - 1]);
+}
 } // namespace Utils
 } // namespace polydeal_hip

@@ -340,6 +340,11 @@ static void record_problem(pdh_ctx *ctx, const pdh_problem *p, const Packed &K)
   ctx->prob.n_rows_owned = (int64_t)K.n_owned * K.n;
   ctx->prob.n_rows_total = p->n_rows;
   ctx->prob.max_row_len = K.max_row_len;
+  ctx->prob.h_blk_ptr = K.blk_ptr;
+  ctx->prob.h_blk_dof = K.blk_dof;
+  ctx->prob.h_slot_dof.resize((size_t)K.n_owned);
+  for (int s = 0; s < K.n_owned; ++s)
+    ctx->prob.h_slot_dof[(size_t)s] = p->dof_offset[K.own_agg[(size_t)s]];
   ctx->prob.n_agg_total = p->n_agg;
   // executed work: k-steps of 4 points per chunk (64 points in k_diag for NT >= 3, else 32; 32 in k_offdiag)
   const int64_t i_sym = sched_instr_rt(K.NT, K.LB, true), i_full = sched_instr_rt(K.NT, K.LB, false);
@@ -488,6 +493,7 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   free_problem(ctx);
   ++ctx->values_gen;
+  ++ctx->problem_epoch;
   struct FreeUnlessDone // every exit before the end leaves no problem resident
   {
     pdh_ctx *ctx;
@@ -608,6 +614,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
     return fail(ctx, PDH_EUNSUPPORTED, "the moment form exists for 3-D bases of degree 1..3 only");
   if (ctx->algorithm == PDH_ALG_ROWS && ctx->prob.row_kernel == RowKernel::none)
     return fail(ctx, PDH_EUNSUPPORTED, "the row kernel does not apply to the resident problem (3-D FE_DGQ / FE_AggloDGP of degree 1 .. 3 on polytopes whose faces are unions of axis-aligned planes, no exchange variant; pdh_check_rows says why)");
+  pr.has_values = true;
   if (ctx->use_rows())
     { // one launch writes everything; reported as kernel 0, kernel 1 takes no time
       hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -1,7 +1,9 @@
 // pdh_capi_transfer.cpp — device driver of the C ABI, level transfers (kernels: pdh_transfer.hip; planner: pdh_transfer_plan.cpp).  A
 // transfer owns its tables on the device of the context it was created on and launches on that context's stream; it needs no resident
-// problem there.
+// problem there.  The Galerkin product of the two levels a transfer connects (kernel: pdh_galerkin.hip; planner: pdh_galerkin_plan.cpp)
+// is the one entry that does: it reads the resident rows of the transfer's context and writes those of the coarse one.
 #include "pdh_ctx.h"
+#include "pdh_galerkin.h"
 #include "pdh_launch.h"
 #include "pdh_transfer.h"
 
@@ -13,8 +15,28 @@ struct pdh_transfer
   PdhTransferArgs args{};
   std::vector<void *> allocs;                              // every hipMalloc of the set-up; args points into these
   DevBuf in{DevBuf::slack}, out{DevBuf::slack};            // staging copies of pdh_prolongate / pdh_restrict
+  // pdh_galerkin_device: host copies of what its planner reads of the description, and the plan on the device - valid for the coarse
+  // context and the two problems (pdh_ctx::problem_epoch) it was built for
+  int degree = 0;
+  std::vector<int32_t> parent, fine_off, coarse_off;
+  std::vector<double> h_tab; // the tables as uploaded: the product applies its own copy of them (pdh_galerkin_tables)
+  struct Galerkin
+  {
+    pdh_ctx *coarse = nullptr;
+    uint64_t fine_epoch = 0, coarse_epoch = 0;
+    std::vector<void *> allocs;
+    PdhGalerkinArgs args{};
+    void drop()
+    {
+      for (void *d : allocs)
+        (void)hipFree(d);
+      allocs.clear();
+      coarse = nullptr;
+    }
+  } gal;
   ~pdh_transfer()
   {
+    gal.drop();
     for (void *d : allocs)
       (void)hipFree(d);
   }
@@ -35,10 +57,15 @@ extern "C" int pdh_transfer_create(pdh_ctx *ctx, const pdh_transfer_desc *d, pdh
   t->n1d = d->degree + 1;
   t->n_fine_rows = d->n_fine_rows;
   t->n_coarse_rows = d->n_coarse_rows;
+  t->degree = d->degree;
+  t->parent.assign(d->parent, d->parent + d->n_fine);
+  t->fine_off.assign(d->fine_dof_offset, d->fine_dof_offset + d->n_fine);
+  t->coarse_off.assign(d->coarse_dof_offset, d->coarse_dof_offset + d->n_coarse);
   PdhTransferArgs &A = t->args;
   A.n_fine = d->n_fine;
   A.n_coarse = d->n_coarse;
   int rc = upload_in(ctx, t->allocs, plan.tab.data(), plan.tab.size(), &A.tab, "transfer tables");
+  t->h_tab = std::move(plan.tab);
   if (rc == PDH_OK)
     rc = upload_in(ctx, t->allocs, d->parent, (size_t)d->n_fine, &A.parent, "parent");
   if (rc == PDH_OK)
@@ -152,4 +179,98 @@ extern "C" int pdh_restrict(pdh_transfer *t, const double *fine, double *coarse)
   PDH_TRY(transfer_checks(t, coarse, fine));
   return staged(t, "pdh_restrict", fine, t->n_fine_rows, coarse, t->n_coarse_rows,
                 [&](const double *d_f, double *d_c) { return pdh_restrict_device(t, d_f, d_c); });
+}
+
+// ---- the Galerkin product ----
+static pdh_galerkin_level galerkin_level(const pdh_ctx *ctx)
+{
+  const pdh_ctx::Problem &pr = ctx->prob;
+  pdh_galerkin_level L;
+  L.n_slots = pr.n_owned;
+  L.n_rows_owned = (int32_t)pr.n_rows_owned;
+  L.n_rows = (int32_t)pr.n_rows_total;
+  L.exchange_mode = pr.ghost ? PDH_EXCHANGE_GHOST : PDH_EXCHANGE_NONE;
+  L.device = ctx->device;
+  L.blk_ptr = pr.h_blk_ptr.data();
+  L.blk_dof = pr.h_blk_dof.data();
+  L.dof_offset = pr.h_slot_dof.data();
+  return L;
+}
+
+// the plan of (t, coarse) on the device: kept while both problems are the ones it was built for
+static int galerkin_plan(pdh_transfer *t, pdh_ctx *coarse)
+{
+  pdh_ctx *fine = t->ctx;
+  pdh_transfer::Galerkin &G = t->gal;
+  if (G.coarse == coarse && G.fine_epoch == fine->problem_epoch && G.coarse_epoch == coarse->problem_epoch)
+    return PDH_OK;
+  G.drop();
+  const pdh_galerkin_level Lf = galerkin_level(fine), Lc = galerkin_level(coarse);
+  const PdhGalerkinPair T{t->dim, t->degree, t->args.n_fine, t->args.n_coarse, t->n_fine_rows, t->n_coarse_rows, t->parent.data(),
+                          t->fine_off.data(), t->coarse_off.data()};
+  PdhGalerkinPlan plan;
+  PDH_TRY(pdh_plan_galerkin(fine->err, T, &Lf, &Lc, plan));
+  if (fine->prob.dev.n != coarse->prob.dev.n || fine->prob.dev.n1d != t->n1d || fine->prob.dev.dim != t->dim ||
+      coarse->prob.dev.n1d != t->n1d || coarse->prob.dev.dim != t->dim)
+    return fail(fine, PDH_EINVAL, "the element of the transfer and those of the two resident problems differ");
+  PdhGalerkinArgs &A = G.args;
+  A = PdhGalerkinArgs{};
+  A.n_blocks = (int32_t)plan.blk_slot.size();
+  std::vector<double> tab(t->h_tab.size());
+  pdh_galerkin_tables(t->n1d, (size_t)t->args.n_fine * t->dim, t->h_tab.data(), tab.data());
+  int rc = upload_in(fine, G.allocs, tab.data(), tab.size(), &A.tab, "Galerkin tables");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.ptr.data(), plan.ptr.size(), &A.plan_ptr, "Galerkin plan");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.slot.data(), plan.slot.size(), &A.plan_slot, "Galerkin plan: slots");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.pos.data(), plan.pos.size(), &A.plan_pos, "Galerkin plan: positions");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.col.data(), plan.col.size(), &A.plan_col, "Galerkin plan: column polytopes");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.blk_slot.data(), plan.blk_slot.size(), &A.blk_slot, "Galerkin plan: coarse slots");
+  if (rc == PDH_OK)
+    rc = upload_in(fine, G.allocs, plan.blk_pos.data(), plan.blk_pos.size(), &A.blk_pos, "Galerkin plan: coarse positions");
+  if (rc != PDH_OK)
+    {
+      G.drop();
+      return rc;
+    }
+  G.coarse = coarse;
+  G.fine_epoch = fine->problem_epoch;
+  G.coarse_epoch = coarse->problem_epoch;
+  return PDH_OK;
+}
+
+extern "C" int pdh_galerkin_device(pdh_transfer *t, pdh_ctx *coarse)
+{
+  if (!t)
+    return fail(nullptr, PDH_EINVAL, "transfer is NULL");
+  pdh_ctx *fine = t->ctx;
+  if (!coarse)
+    return fail(fine, PDH_EINVAL, "pdh_galerkin_device: the coarse context is NULL");
+  if (coarse == fine)
+    return fail(fine, PDH_EINVAL, "pdh_galerkin_device: the coarse context is the transfer's own");
+  if (!fine->prob.resident)
+    return fail(fine, PDH_ESTATE, "pdh_galerkin_device called before pdh_set_problem on the fine context");
+  if (!fine->prob.has_values)
+    return fail(fine, PDH_ESTATE, "pdh_galerkin_device: the values of the fine context were never assembled");
+  if (!coarse->prob.resident)
+    return fail(fine, PDH_ESTATE, "pdh_galerkin_device called before pdh_set_problem on the coarse context");
+  PDH_HIP(fine, hipSetDevice(fine->device));
+  PDH_TRY(galerkin_plan(t, coarse));
+  // whatever reads or writes the coarse values on the coarse context's stream, and the fine values on the fine one's, is over first
+  PDH_HIP(fine, hipStreamSynchronize(coarse->stream));
+  PdhGalerkinArgs A = t->gal.args;
+  const pdh_ctx::Problem &pf = fine->prob, &pc = coarse->prob;
+  A.fine_values = pf.dev.values;
+  A.coarse_values = pc.dev.values;
+  A.f_row_base = pf.dev.row_base, A.f_row_len = pf.dev.row_len, A.f_diag_L = pf.dev.diag_L;
+  A.c_row_base = pc.dev.row_base, A.c_row_len = pc.dev.row_len, A.c_diag_L = pc.dev.diag_L;
+  A.f_diag_first = pf.dev.diag_first, A.c_diag_first = pc.dev.diag_first;
+  ++coarse->values_gen;
+  PDH_HIP(fine, pdh_launch_galerkin(t->dim, t->n1d, &A, fine->stream));
+  PDH_HIP(fine, hipStreamSynchronize(fine->stream));
+  coarse->prob.has_values = true;
+  return PDH_OK;
 }

@@ -91,6 +91,7 @@ struct pdh_ctx
   // preconditioner set up last is checked; the caller's choice of it outlives a problem so that solving after a new
   // pdh_set_problem answers "set it up again" (its data - Problem::Solver - does not)
   uint64_t values_gen = 0, prec_gen = 0;
+  uint64_t problem_epoch = 0; // counts the pdh_set_problem* calls: what a cached plan of two contexts' problems is checked against
   int prec_kind = PDH_PREC_NONE;
   bool prec_ok = true;
   // prec_epoch counts the set-up calls (a pdh_mg records it per level: the same kind set up again on the same values is a change too);
@@ -172,6 +173,11 @@ struct pdh_ctx
     const int64_t *d_blk_ptr = nullptr;
     const int32_t *d_blk_dof = nullptr;
     int max_row_len = 0;
+    // host copies of the block lists and of the first dof of every owned slot's polytope, for the planner of the Galerkin product
+    // (pdh_galerkin.h); has_values: the values were written at least once (pdh_assemble_device, pdh_galerkin_device)
+    std::vector<int64_t> h_blk_ptr;
+    std::vector<int32_t> h_blk_dof, h_slot_dof;
+    bool has_values = false;
     struct Solver
     {
       DevBuf dinv, flag, r, z, p, q, part, scal, cheb_d, cheb_r;

@@ -16,6 +16,7 @@
 #include "pdh_terms_tables.h"
 
 struct PdhTransferArgs; // pdh_transfer.h
+struct PdhGalerkinArgs; // pdh_galerkin.h
 
 // One resolved launch (host only).  kernel: host stub of the instantiation, NULL where nothing could be resolved (no such instantiation,
 // a grid beyond 2^31 - 1 blocks) - launching that answers hipErrorInvalidValue; grid 0: nothing to do, a successful no-op.
@@ -163,4 +164,8 @@ hipError_t pdh_launch_prolongate(int dim, int n1d, int add, const PdhTransferArg
 hipError_t pdh_launch_restrict(int dim, int n1d, int add, const PdhTransferArgs *A, const double *fine, double *coarse, hipStream_t stream);
 // r = b - r over n_rows entries (r holds A x)
 hipError_t pdh_launch_residual_sub(int64_t n_rows, const double *b, double *r, hipStream_t stream);
+
+// pdh_galerkin.hip (dim 2, n1d 2 .. 8 | dim 3, n1d 2 .. 4: at most 64 dofs per polytope)
+// coarse values = P^T (fine values) P: one wave per coarse block, its fine blocks in plan order
+hipError_t pdh_launch_galerkin(int dim, int n1d, const PdhGalerkinArgs *A, hipStream_t stream);
 }

@@ -122,15 +122,26 @@ class MultigridHierarchy:
         self.contexts = []
 
 
+def _setup_level(ctx, l, inner, degree, smoother_precision):
+    """the solver of level 0, the smoother of every level above: what its set-up reported"""
+    info = ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree)
+    if l > 0 and smoother_precision == "f32":
+        ctx.set_smoother_precision("f32")
+    return info
+
+
 def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = None, diag_first=True, degree=3, inner=None, device=0,
-                        smoother_precision="f64"):
+                        smoother_precision="f64", coarse_operators="assembled"):
     """The reference's agglomerated multigrid (examples/simplex_agglomerated_multigrid.cc:378-515) on one device: one context per level
     handler of `levels` (coarse to fine, e.g. block_hierarchy's), each assembled like assemble_levels does (the Cartesian description
     where it is taken); Chebyshev of `degree` over `inner` ('block_jacobi' up to 64 dofs per polytope, 'jacobi' above, unless given) as
     the smoother of every level above the coarsest, the dense direct solve on the coarsest (at most 1024 rows), the level transfers
     and the V-cycle, which becomes the preconditioner of the finest context.  smoother_precision 'f32': every level above the coarsest
     smooths, and forms its residual, with a float32 copy of its matrix (Context.set_smoother_precision); CG and all vectors stay double.
-    Returns a MultigridHierarchy; close() it."""
+    coarse_operators 'galerkin': only the finest level is assembled, every level below it gets A_(l-1) = P^T A_l P from the level above
+    (Transfer.galerkin_device, the reference's AmgProjector::compute_level_matrices, include/multigrid_amg.h:267-305), fine to coarse,
+    before any level is set up; at most 64 dofs per polytope.  'assembled' (default): every level assembles the SIP operator on its own
+    polytopes.  Returns a MultigridHierarchy; close() it."""
     from ._capi import Context, Multigrid, PdhError
     from .handler import HostError
 
@@ -139,6 +150,9 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
         inner = "block_jacobi" if fe.n_dofs_per_cell <= 64 else "jacobi"
     if smoother_precision not in ("f64", "f32"):
         raise ValueError("smoother_precision must be 'f64' or 'f32'")
+    if coarse_operators not in ("assembled", "galerkin"):
+        raise ValueError("coarse_operators must be 'assembled' or 'galerkin'")
+    galerkin = coarse_operators == "galerkin"
     contexts, transfers, info, mg = [], [], [], None
     try:
         for l, ah in enumerate(levels):
@@ -156,12 +170,16 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
             if flat is None:
                 flat = ah.flatten(variant, diag_first, False)  # (no colind: nothing here reads the pattern back)
                 ctx.set_problem(flat)
-            ctx.assemble_device()
-            info.append(ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree))
-            if l > 0 and smoother_precision == "f32":
-                ctx.set_smoother_precision("f32")
+            if not galerkin:
+                ctx.assemble_device()
+                info.append(_setup_level(ctx, l, inner, degree, smoother_precision))
             if l > 0:
                 transfers.append(level_transfer(ctx, levels[l - 1], ah))
+        if galerkin:
+            contexts[-1].assemble_device()
+            for l in range(len(levels) - 1, 0, -1):
+                transfers[l - 1].galerkin_device(contexts[l - 1])
+            info = [_setup_level(ctx, l, inner, degree, smoother_precision) for l, ctx in enumerate(contexts)]
         mg = Multigrid(contexts, transfers)
     except Exception:
         MultigridHierarchy(contexts, transfers, mg, info).close()

@@ -29,6 +29,11 @@ launches restricted to the finest level (pre-smoothing from zero, residual, post
 their difference is what the coarser levels cost; (c) the solve b = A x*, rel_tol 1e-13, with block Jacobi and with the V-cycle at
 smoother degrees 2, 3 and 5: iterations, products with the finest A, seconds.  No condition is checked: the table is the result.
 
+Galerkin section (--vcycle --galerkin, alone; pdh_galerkin_device), written to profiles/r11_galerkin.json unless --out says otherwise, on
+the hierarchy of the V-cycle section, ONE process, HIP events, medians of --reps: k_galerkin per level pair and summed, k_vmult of the finest
+matrix (the yardstick: it reads the same bytes once), wall time of the whole Galerkin set-up - first call with the plans, and later calls -
+against assembling the coarser levels, and the headline V-cycle solve on the Galerkin and on the assembled hierarchy, alternating twice each.
+
 Single-precision smoother section (--vcycle --smoother-f32, or --chebyshev --smoother-f32, alone; pdh_set_smoother_precision), written to
 profiles/r10_smoother_f32.json unless --out says otherwise (the --chebyshev form writes only where --out says).  Everything in ONE process,
 the F64 path measured there being the yardstick: k_vmult against k_vmult_f32 on the finest matrix, alternating, in ms and in TB/s of the
@@ -350,6 +355,94 @@ def vcycle_case(pa, torch, cells, reps):
     return out
 
 
+def galerkin_case(pa, torch, cells, reps):
+    """the Galerkin figures: see the module docstring"""
+    from polydeal_amd._capi import Multigrid
+    from polydeal_amd.levels import block_hierarchy, multigrid_hierarchy
+
+    t0 = time.time()
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    fe = pa.FE_DGQ(3, 3)
+    blocks = [b for b in (32, 16, 8, 4, 2) if 2 * b <= cells]
+    handlers = block_hierarchy(grid, fe, blocks)
+    w0 = time.perf_counter()
+    hier = multigrid_hierarchy(handlers, fe, pa.SipVariant.poisson_example(fe), diag_first=True, degree=3)
+    set_up_wall = time.perf_counter() - w0
+    stream = torch.cuda.current_stream().cuda_stream
+    for c in hier.contexts:
+        c.set_stream(stream)
+    ctxs, trs, fin = hier.contexts, hier.transfers, hier.finest
+    hier.mg.close()
+    hier.mg = None
+    N = handlers[-1].n_dofs
+    values = [c.stats()["n_values"] for c in ctxs]
+    out = {"element": "FE_DGQ(3)", "cells_per_axis": cells, "blocks": blocks, "polytopes": [h.n_agglomerates for h in handlers],
+           "rows": [h.n_dofs for h in handlers], "n_values": values, "assembled_hierarchy_set_up_wall_s": set_up_wall,
+           "note": "the coarse contexts go through pdh_set_problem like any other: their assembly set-up (points, tables, launches) is "
+                   "paid inside assembled_hierarchy_set_up_wall_s and is not used by the Galerkin product"}
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        w = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - w) * 1e3
+
+    def galerkin_all():
+        for l in range(len(ctxs) - 1, 0, -1):
+            trs[l - 1].galerkin_device(ctxs[l - 1])
+
+    def assemble_coarser():
+        for c in ctxs[:-1]:
+            c.assemble_device()
+    # (a) wall time of the set-up: the first round builds the plans, the later ones find them on the transfers
+    first = wall_ms(galerkin_all)
+    later = [wall_ms(galerkin_all) for _ in range(reps)]
+    asm = [wall_ms(assemble_coarser) for _ in range(reps + 1)][1:]
+    out.update(galerkin_set_up_wall_ms_first_call_with_plans=first, galerkin_set_up_wall_ms_median=median(later),
+               assemble_coarser_levels_wall_ms_median=median(asm))
+    # (b) the kernel per pair (events round the call: one kernel on the stream) and k_vmult of the finest matrix in the same process
+    x, y = torch.rand(N, dtype=torch.float64, device="cuda"), torch.empty(N, dtype=torch.float64, device="cuda")
+    vm = event_times_ms(torch, lambda: fin.vmult_device(x.data_ptr(), y.data_ptr()), reps)
+    galerkin_all()  # every level holds the product of the level above, as in the set-up
+    pairs = []
+    for l in range(len(ctxs) - 1, 0, -1):
+        t = event_times_ms(torch, lambda: trs[l - 1].galerkin_device(ctxs[l - 1]), reps)
+        pairs.append({"fine_polytopes": handlers[l].n_agglomerates, "coarse_polytopes": handlers[l - 1].n_agglomerates,
+                      "fine_bytes": 8.0 * values[l], "k_galerkin_ms_median": median(t), "k_galerkin_ms_min": min(t),
+                      "fine_read_TBps": 8.0 * values[l] / (median(t) * 1e-3) / 1e12})
+    vm2 = event_times_ms(torch, lambda: fin.vmult_device(x.data_ptr(), y.data_ptr()), reps)
+    k_vm = median(vm + vm2)
+    out.update(pairs=pairs, k_vmult_finest_ms_median=k_vm, k_galerkin_finest_pair_ms_median=pairs[0]["k_galerkin_ms_median"],
+               k_galerkin_all_pairs_ms=sum(p["k_galerkin_ms_median"] for p in pairs),
+               k_galerkin_finest_pair_over_k_vmult=pairs[0]["k_galerkin_ms_median"] / k_vm, expected_ratio_at_most=4.0)
+    # (c) the headline V-cycle solve, Galerkin against assembled hierarchy, alternating twice each
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=gen)
+    rhs = torch.empty(N, dtype=torch.float64, device="cuda")
+    fin.vmult_device(xs.data_ptr(), rhs.data_ptr())
+    out["solves"] = []
+    for kind in ("galerkin", "assembled", "galerkin", "assembled"):
+        galerkin_all() if kind == "galerkin" else assemble_coarser()
+        for l, c in enumerate(ctxs):
+            c.setup_direct() if l == 0 else c.setup_chebyshev("block_jacobi", degree=3)
+        mg = Multigrid(ctxs, trs)
+        sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        w = time.perf_counter()
+        si = fin.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+        wall = time.perf_counter() - w
+        its = si["iterations"]
+        out["solves"].append({"coarse_operators": kind, "iterations": its, "products_with_finest_A": 1 + (its + 1) * 2 * 3 + its,
+                              "wall_s": wall, "residual": si["residual"],
+                              "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))})
+        print(json.dumps(out["solves"][-1]), flush=True)
+        mg.close()
+    out["case_wall_s"] = time.time() - t0
+    hier.close()
+    return out
+
+
 def vmult_bytes(st, n, N, f32):
     """what one product must move: the values, the x gathered per slot (row_len doubles), blk_dof per block and the per-slot arrays
     (row_base, row_len, diag_L, own_row, blk_ptr; the shadow adds its base), and y"""
@@ -497,11 +590,24 @@ def main():
     ap.add_argument("--vcycle", action="store_true", help="the V-cycle section alone (default --out: profiles/r09_vcycle.json)")
     ap.add_argument("--smoother-f32", action="store_true",
                     help="with --vcycle or --chebyshev: the single-precision smoother section alone (--vcycle: default --out profiles/r10_smoother_f32.json)")
+    ap.add_argument("--galerkin", action="store_true",
+                    help="with --vcycle: the Galerkin-product section alone (default --out: profiles/r11_galerkin.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.galerkin:
+        if not args.vcycle or args.smoother_f32:
+            ap.error("--galerkin goes with --vcycle alone")
+        out = {"tool": "tools/solve_bench.py --vcycle --galerkin", "version": pa.load_library().pdh_version().decode(),
+               "device": torch.cuda.get_device_name(0)}
+        out.update(galerkin_case(pa, torch, args.cells, args.reps))
+        doc = json.dumps(out, indent=1)
+        with open(args.out or os.path.join(ROOT, "profiles", "r11_galerkin.json"), "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     if args.smoother_f32:
         if not (args.vcycle or args.chebyshev):
             ap.error("--smoother-f32 goes with --vcycle or --chebyshev")
