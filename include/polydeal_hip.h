@@ -586,6 +586,42 @@ int pdh_set_smoother_precision(pdh_ctx *ctx, int precision);
 int pdh_smoother_precision(pdh_ctx *ctx);
 int pdh_smoother_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y);
 
+/* Matrix-free SIP operator (pdh_matfree.h).  On agglomerates of Cartesian cells every block of the matrix is a short sum of Kronecker
+ * products of three 1-D matrices per (merged) cell or sub-face, so y = A x can be formed by sum factorisation from those 1-D matrices
+ * alone - a few hundred doubles per polytope where its rows are tens of thousands - in double precision, reading no stored value.
+ *   pdh_setup_matrix_free builds the tables of every owned polytope on the device, once per resident problem (a second call only fills
+ * `info`); they live and die with the problem and do not depend on the values, assembled or not.  It needs a problem whose plan chose
+ * the term kernels (pdh_rows_kernel_in_use == PDH_ROWS_TERMS under PDH_ALG_AUTO: 3-D FE_DGQ / FE_AggloDGP of degree 1 .. 3, axis-aligned
+ * cells with tensor rules, no PDH_EXCHANGE_GHOST, PDH_TERMS not 0); anything else is PDH_EUNSUPPORTED naming the reason.
+ *   pdh_matrix_free_vmult / _device: y = A x with the vectors and rules of pdh_vmult / pdh_vmult_device (x in the global numbering, ghost
+ * columns read from it; x and y disjoint, else PDH_EINVAL); PDH_ESTATE before pdh_setup_matrix_free.  A is the SIP operator of the
+ * resident description as pdh_assemble_device would write it, up to rounding (another order of summation; a sub-face plane that lies on
+ * a box face is taken from the box, not from a face point, which far from the origin is the more exact).  Fixed order, no atomics:
+ * the same call gives the same bits.
+ *   pdh_set_smoother_operator(PDH_SMOOTHER_OP_MATRIX_FREE): every product of the Chebyshev application of this context - on its own,
+ * inside CG, as the smoother of this level inside a V-cycle - and the residual of this level inside a V-cycle come from the tables.
+ * pdh_vmult*, pdh_residual_device, CG's own A p, the eigenvalue estimate, the block inverses and the dense gather keep reading the stored
+ * values: the split pdh_set_smoother_precision makes, and orthogonal to it - with MATRIX_FREE the products ignore the shadow rows, the
+ * precision still decides which block inverses the update reads.  State rules as for the precision: PDH_PREC_CHEBYSHEV set up and
+ * current (else PDH_ESTATE), the tables set up (else PDH_ESTATE), no PDH_PREC_MULTIGRID attached (PDH_ESTATE: choose per level BEFORE
+ * pdh_mg_create); it counts as a set-up call for a pdh_mg that holds the context; every pdh_setup_preconditioner / _chebyshev / _direct
+ * goes back to STORED.  The tables are the operator of the DESCRIPTION: while the values were last written by pdh_galerkin_device, or
+ * never assembled, MATRIX_FREE is PDH_ESTATE, and a later pdh_galerkin_device into the context puts it back to STORED.
+ *   pdh_smoother_operator: the one in force (< 0 on error).                                                                            */
+typedef struct pdh_matrix_free_info
+{
+  int64_t table_bytes;          /* device memory of the tables */
+  int32_t doubles_per_polytope; /* stride of a polytope's record */
+  int32_t max_cells, max_subfaces, max_interior_subfaces; /* of one owned polytope, after merging */
+} pdh_matrix_free_info;
+int pdh_setup_matrix_free(pdh_ctx *ctx, pdh_matrix_free_info *info /* may be NULL */);
+int pdh_matrix_free_vmult(pdh_ctx *ctx, const double *x, double *y);             /* host pointers */
+int pdh_matrix_free_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y);  /* queued on the context's stream */
+#define PDH_SMOOTHER_OP_STORED 0
+#define PDH_SMOOTHER_OP_MATRIX_FREE 1
+int pdh_set_smoother_operator(pdh_ctx *ctx, int op);
+int pdh_smoother_operator(pdh_ctx *ctx);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

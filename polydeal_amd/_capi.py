@@ -22,6 +22,8 @@ PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI, PDH_PREC_CHEBYSHEV, PDH_P
 _PREC = {"none": PDH_PREC_NONE, "jacobi": PDH_PREC_JACOBI, "block_jacobi": PDH_PREC_BLOCK_JACOBI}
 PDH_SMOOTHER_F64, PDH_SMOOTHER_F32 = 0, 1
 _SMOOTHER = {"f64": PDH_SMOOTHER_F64, "f32": PDH_SMOOTHER_F32}
+PDH_SMOOTHER_OP_STORED, PDH_SMOOTHER_OP_MATRIX_FREE = 0, 1
+_SMOOTHER_OP = {"stored": PDH_SMOOTHER_OP_STORED, "matrix_free": PDH_SMOOTHER_OP_MATRIX_FREE}
 CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
 
@@ -51,6 +53,11 @@ class pdh_chebyshev_info(C.Structure):
 
 class pdh_direct_info(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("pivot_min", C.c_double), ("pivot_max", C.c_double)]
+
+
+class pdh_matrix_free_info(C.Structure):
+    _fields_ = [("table_bytes", C.c_int64), ("doubles_per_polytope", C.c_int32), ("max_cells", C.c_int32), ("max_subfaces", C.c_int32),
+                ("max_interior_subfaces", C.c_int32)]
 
 
 class _Opaque(C.c_void_p):
@@ -118,6 +125,7 @@ EXPORTS = [
     "pdh_setup_direct", "pdh_mg_create", "pdh_mg_destroy", "pdh_mg_vcycle_device",
     "pdh_set_smoother_precision", "pdh_smoother_precision", "pdh_smoother_vmult_device",
     "pdh_galerkin_plan", "pdh_galerkin_device",
+    "pdh_setup_matrix_free", "pdh_matrix_free_vmult", "pdh_matrix_free_vmult_device", "pdh_set_smoother_operator", "pdh_smoother_operator",
 ]
 
 # (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
@@ -220,7 +228,23 @@ def _bind(lib):
     lib.pdh_galerkin_plan.argtypes = [P(pdh_transfer_desc), P(pdh_galerkin_level), P(pdh_galerkin_level), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pdh_galerkin_device.argtypes = [pdh_transfer_p, pdh_ctx_p]
     lib.pdh_galerkin_matrices_1d.argtypes = [P(pdh_transfer_desc), C.c_void_p]
+    lib.pdh_setup_matrix_free.argtypes = [pdh_ctx_p, P(pdh_matrix_free_info)]
+    lib.pdh_matrix_free_vmult.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
+    lib.pdh_matrix_free_vmult_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
+    lib.pdh_set_smoother_operator.argtypes = [pdh_ctx_p, C.c_int]
+    lib.pdh_smoother_operator.argtypes = [pdh_ctx_p]
     return real
+
+
+def smoother_operator_code(op):
+    """PDH_SMOOTHER_OP_* of 'stored' | 'matrix_free' (or of the code itself); ValueError for anything else"""
+    if isinstance(op, str):
+        if op not in _SMOOTHER_OP:
+            raise ValueError("smoother operator must be 'stored' or 'matrix_free'")
+        return _SMOOTHER_OP[op]
+    if int(op) not in _SMOOTHER_OP.values():
+        raise ValueError("smoother operator must be PDH_SMOOTHER_OP_STORED or PDH_SMOOTHER_OP_MATRIX_FREE")
+    return int(op)
 
 
 def tridiagonal_eigenvalues(diag, offdiag):
@@ -672,6 +696,42 @@ class Context:
     def smoother_vmult_device(self, d_x, d_y):
         """y = A~ x with the float32 copy of the matrix ('f32' in force); device pointers (ints), asynchronous on the context's stream."""
         self._chk(self.lib.pdh_smoother_vmult_device(self.h, C.c_void_p(d_x), C.c_void_p(d_y)))
+
+    def setup_matrix_free(self):
+        """The 1-D tables of the matrix-free SIP operator, built on the device once per resident problem (pdh_setup_matrix_free; needs the
+        term kernels' plan, else PdhError PDH_EUNSUPPORTED): what the set-up reports."""
+        info = pdh_matrix_free_info()
+        self._chk(self.lib.pdh_setup_matrix_free(self.h, C.byref(info)))
+        return {"table_bytes": int(info.table_bytes), "doubles_per_polytope": int(info.doubles_per_polytope),
+                "max_cells": int(info.max_cells), "max_subfaces": int(info.max_subfaces),
+                "max_interior_subfaces": int(info.max_interior_subfaces)}
+
+    def matrix_free_vmult(self, x):
+        """A x for the owned rows from the tables, no stored value read; x [n_rows] in the global dof numbering."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.shape != (self.n_rows,):
+            raise ValueError("x must have n_rows = %d entries" % self.n_rows)
+        y = np.empty(self.n_rows_owned)
+        self._chk(self.lib.pdh_matrix_free_vmult(self.h, xx.ctypes.data, y.ctypes.data))
+        return y
+
+    def matrix_free_vmult_device(self, d_x, d_y):
+        """Device pointers (ints); asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_matrix_free_vmult_device(self.h, C.c_void_p(d_x), C.c_void_p(d_y)))
+
+    def set_smoother_operator(self, op):
+        """'stored' | 'matrix_free' (or PDH_SMOOTHER_OP_*): with 'matrix_free' the products of the Chebyshev smoother set up last, and the
+        residual of this level inside a V-cycle, come from the tables of setup_matrix_free instead of the stored values
+        (pdh_set_smoother_operator).  Every setup_* call goes back to 'stored'."""
+        self._chk(self.lib.pdh_set_smoother_operator(self.h, smoother_operator_code(op)))
+
+    @property
+    def smoother_operator(self):
+        """'stored' | 'matrix_free': the one in force"""
+        rc = self.lib.pdh_smoother_operator(self.h)
+        if rc < 0:
+            self._chk(rc)
+        return {v: k for k, v in _SMOOTHER_OP.items()}[rc]
 
     def chebyshev_step_device(self, d_b, d_x, zero_initial_guess=False):
         """One application of the smoother to b from the x in d_x (device pointers as ints); asynchronous on the context's stream."""

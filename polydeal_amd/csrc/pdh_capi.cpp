@@ -544,6 +544,7 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
       lap("upload: term kernel state");
     }
   ctx->prob.row_kernel = plan->kernel;
+  ctx->prob.why_terms = plan->why_terms;
   // 4. the launches of every form of the problem
   resolve_launches(ctx, K, sw, cus);
   ctx->prob.resident = true;
@@ -615,6 +616,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
   if (ctx->algorithm == PDH_ALG_ROWS && ctx->prob.row_kernel == RowKernel::none)
     return fail(ctx, PDH_EUNSUPPORTED, "the row kernel does not apply to the resident problem (3-D FE_DGQ / FE_AggloDGP of degree 1 .. 3 on polytopes whose faces are unions of axis-aligned planes, no exchange variant; pdh_check_rows says why)");
   pr.has_values = true;
+  pr.galerkin_values = false;
   if (ctx->use_rows())
     { // one launch writes everything; reported as kernel 0, kernel 1 takes no time
       hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

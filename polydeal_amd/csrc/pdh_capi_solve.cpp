@@ -56,13 +56,19 @@ static int all_rows_checks(pdh_ctx *ctx, const char *who, const char *runs_on, c
   return PDH_OK;
 }
 
-static int vmult_checks(pdh_ctx *ctx, const void *x, const void *y)
+int pdh_vmult_vectors_check(pdh_ctx *ctx, const char *name, const void *x, const void *y)
 {
-  PDH_TRY(need_problem(ctx, "pdh_vmult"));
+  PDH_TRY(need_problem(ctx, name));
   if (!x || !y)
     return fail(ctx, PDH_EINVAL, "x and y are required");
   if (overlap(x, ctx->prob.n_rows_total, y, ctx->prob.n_rows_owned))
     return fail(ctx, PDH_EINVAL, "x and y overlap");
+  return PDH_OK;
+}
+
+static int vmult_checks(pdh_ctx *ctx, const void *x, const void *y)
+{
+  PDH_TRY(pdh_vmult_vectors_check(ctx, "pdh_vmult", x, y));
   return pdh_row_fits_lds(ctx);
 }
 
@@ -111,7 +117,8 @@ static void new_setup(pdh_ctx *ctx)
   pdh_mg_detach(ctx);
   ctx->mg_gone = false;
   ++ctx->prec_epoch;
-  ctx->prob.sol.f32 = false; // the smoother precision belongs to one set-up (pdh_set_smoother_precision)
+  ctx->prob.sol.f32 = false; // the smoother precision and operator belong to one set-up (pdh_set_smoother_precision / _operator)
+  ctx->prob.sol.matrix_free = false;
 }
 
 extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
@@ -493,6 +500,13 @@ extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double
 int pdh_smoother_vmult(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *x, double *y, hipStream_t stream)
 {
   const pdh_ctx::Problem::Solver &S = ctx->prob.sol;
+  if (S.matrix_free)
+    { // PDH_SMOOTHER_OP_MATRIX_FREE: neither the values nor the shadow rows are read
+      if (!ctx->prob.d_mf_tables)
+        return fail(report, PDH_ESTATE, "the matrix-free operator is not set up");
+      PDH_HIP(report, pdh_launch_mf_vmult(&A, ctx->prob.dev.n1d, &ctx->prob.terms, ctx->prob.d_mf_tables, x, y, nullptr, stream));
+      return PDH_OK;
+    }
   if (!S.f32)
     {
       PDH_HIP(report, pdh_launch_vmult(&A, x, y, nullptr, stream));
@@ -581,7 +595,45 @@ extern "C" int pdh_smoother_vmult_device(pdh_ctx *ctx, const double *d_x, double
   if (ctx->prec_gen != ctx->values_gen)
     return fail(ctx, PDH_ESTATE, "the values changed since pdh_set_smoother_precision: set the smoother up again");
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  return pdh_smoother_vmult(ctx, ctx, pdh_solve_args(ctx), d_x, d_y, ctx->stream);
+  const PdhSolveArgs A = pdh_solve_args(ctx);
+  const pdh_ctx::Problem::Solver &S = ctx->prob.sol; // (the shadow on its own, whichever operator the smoother applies)
+  const PdhShadowArgs Sh{S.sh_values.ptr<float>(), S.sh_base.ptr<int64_t>()};
+  PDH_HIP(ctx, pdh_launch_vmult_f32(&A, &Sh, d_x, d_y, ctx->stream));
+  return PDH_OK;
+}
+
+// ---- the operator of the smoother's products (include/polydeal_hip.h: pdh_set_smoother_operator; kernels: pdh_matfree.h) ----------------
+extern "C" int pdh_set_smoother_operator(pdh_ctx *ctx, int op)
+{
+  PDH_TRY(need_problem(ctx, "pdh_set_smoother_operator"));
+  if (op != PDH_SMOOTHER_OP_STORED && op != PDH_SMOOTHER_OP_MATRIX_FREE)
+    return fail(ctx, PDH_EINVAL, "pdh_set_smoother_operator: op must be PDH_SMOOTHER_OP_STORED or PDH_SMOOTHER_OP_MATRIX_FREE");
+  if (ctx->prec_kind == PDH_PREC_MULTIGRID)
+    return fail(ctx, PDH_ESTATE, "pdh_set_smoother_operator: the context has a multigrid preconditioner attached; choose the operator of "
+                                 "every level before pdh_mg_create");
+  if (ctx->prec_kind != PDH_PREC_CHEBYSHEV || ctx->mg_gone)
+    return fail(ctx, PDH_ESTATE, "pdh_set_smoother_operator: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
+  PDH_TRY(prec_checks(ctx));
+  if (op == PDH_SMOOTHER_OP_MATRIX_FREE)
+    {
+      if (!ctx->prob.d_mf_tables)
+        return fail(ctx, PDH_ESTATE, "pdh_set_smoother_operator: the matrix-free operator is not set up (pdh_setup_matrix_free)");
+      // the tables are the SIP assembly of the resident description: they do not stand for values written by anything else
+      if (!ctx->prob.has_values || ctx->prob.galerkin_values)
+        return fail(ctx, PDH_ESTATE, ctx->prob.galerkin_values
+                                       ? "pdh_set_smoother_operator: the values of this context were written by pdh_galerkin_device; the "
+                                         "matrix-free operator is the SIP assembly of the resident description"
+                                       : "pdh_set_smoother_operator: the values of this context were never assembled");
+    }
+  ctx->prob.sol.matrix_free = op == PDH_SMOOTHER_OP_MATRIX_FREE;
+  ++ctx->prec_epoch;
+  return PDH_OK;
+}
+
+extern "C" int pdh_smoother_operator(pdh_ctx *ctx)
+{
+  PDH_TRY(need_problem(ctx, "pdh_smoother_operator"));
+  return ctx->prob.sol.matrix_free ? PDH_SMOOTHER_OP_MATRIX_FREE : PDH_SMOOTHER_OP_STORED;
 }
 
 // ---- dense direct solve (include/polydeal_hip.h: pdh_setup_direct; steps and layout: pdh_dense.h) ---------------------------------------

@@ -272,5 +272,7 @@ extern "C" int pdh_galerkin_device(pdh_transfer *t, pdh_ctx *coarse)
   PDH_HIP(fine, pdh_launch_galerkin(t->dim, t->n1d, &A, fine->stream));
   PDH_HIP(fine, hipStreamSynchronize(fine->stream));
   coarse->prob.has_values = true;
+  coarse->prob.galerkin_values = true; // (not the SIP assembly of the coarse description: the smoother goes back to the stored operator)
+  coarse->prob.sol.matrix_free = false;
   return PDH_OK;
 }

@@ -1,4 +1,5 @@
-// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_transfer.cpp, pdh_capi_mg.cpp), not
+// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_matfree.cpp, pdh_capi_transfer.cpp,
+// pdh_capi_mg.cpp), not
 // installed: the context
 // behind the opaque pdh_ctx of include/polydeal_hip.h, error reporting, the one device-buffer type, the alloc / upload helpers of
 // set-up and the entry guards.  No kernel header here: pdh_launch.h brings the kernels' argument structs and the launch records.
@@ -178,6 +179,12 @@ struct pdh_ctx
     std::vector<int64_t> h_blk_ptr;
     std::vector<int32_t> h_blk_dof, h_slot_dof;
     bool has_values = false;
+    bool galerkin_values = false; // ... last by pdh_galerkin_device: they are not the SIP assembly of this description
+    // pdh_setup_matrix_free (pdh_matfree.h): the finished 1-D tables of every owned polytope (in `allocs`), valid for the life of the
+    // problem; why_terms: what the planner said where it built no term tables
+    const double *d_mf_tables = nullptr;
+    int64_t mf_table_bytes = 0;
+    std::string why_terms;
     struct Solver
     {
       DevBuf dinv, flag, r, z, p, q, part, scal, cheb_d, cheb_r;
@@ -192,6 +199,7 @@ struct pdh_ctx
       DevBuf sh_values, sh_base, sh_dinv;
       int64_t sh_count = 0; // entries of sh_values once sh_base is filled, 0 before
       bool f32 = false;
+      bool matrix_free = false; // pdh_set_smoother_operator: the same products apply the operator from d_mf_tables
     } sol;
   } prob;
 
@@ -356,12 +364,15 @@ struct Staging
 // pdh_capi_solve.cpp.  The launch helpers take the stream they queue on: the context's own for its entry points, the finest level's
 // for every level of a V-cycle.
 PdhSolveArgs pdh_solve_args(const pdh_ctx *ctx);
+// the guard of the products: a problem resident (`name` in the message), x [n_rows_total] and y [owned rows] given and disjoint
+int pdh_vmult_vectors_check(pdh_ctx *ctx, const char *name, const void *x, const void *y);
 int pdh_row_fits_lds(pdh_ctx *ctx); // PDH_EUNSUPPORTED on `ctx`: a row of more than 8192 entries (k_vmult keeps a column set in LDS)
 // One application of the Chebyshev polynomial of `ctx` to b: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b, x not read).
 // rcg / part: see pdh_launch_cheb_update.  Errors are reported on `report`.
 int pdh_cheb_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *b, double *x, bool zero, const double *rcg, double *part,
                    hipStream_t stream);
-// y = A x as the smoother of `ctx` sees A: the float32 shadow while PDH_SMOOTHER_F32 is in force, else pdh_launch_vmult
+// y = A x as the smoother of `ctx` sees A: from the term tables while PDH_SMOOTHER_OP_MATRIX_FREE is in force, else the float32 shadow
+// while PDH_SMOOTHER_F32 is, else pdh_launch_vmult
 int pdh_smoother_vmult(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *x, double *y, hipStream_t stream);
 // z = P^-1 r with the preconditioner of `ctx` as set up - any kind but PDH_PREC_MULTIGRID, r and z disjoint - without the state checks
 int pdh_prec_apply(pdh_ctx *ctx, pdh_ctx *report, const PdhSolveArgs &A, const double *r, double *z, const double *rcg, double *part,

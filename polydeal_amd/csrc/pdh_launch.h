@@ -104,6 +104,13 @@ PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int w
 hipError_t pdh_launch_terms(const PdhLaunch *L, const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream);
 hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T, double *out, int count, hipStream_t stream);
 
+// pdh_matfree.hip (3-D, n1d 2 .. 4, a problem whose plan built the term tables).  tables: the finished 1-D tables of every owned polytope,
+// count * pdht::matfree_rec_doubles doubles; hipErrorInvalidValue: no such kind
+hipError_t pdh_launch_mf_tables(const PdhDev *P, const PdhTerms *T, double *tables, int count, hipStream_t stream);
+// y[own rows] = A x from the tables, with the vectors and the partial of pdh_launch_vmult
+hipError_t pdh_launch_mf_vmult(const PdhSolveArgs *A, int n1d, const PdhTerms *T, const double *tables, const double *x, double *y,
+                               double *part, hipStream_t stream);
+
 // pdh_tiled.hip: L[0] own blocks, symmetric tiles ti == tj, L[1] coupling blocks, L[2] own blocks, pairs ti < tj (none of the own
 // blocks resolves if one of the two grids is too large)
 void pdh_resolve_tiled(int dim, int n1d, int n, bool reaction, int n_own, int n_items, PdhLaunch *L);

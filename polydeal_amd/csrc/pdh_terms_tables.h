@@ -115,6 +115,20 @@ PDH_HD constexpr int terms_task_doubles(int maxsf, int maxcell, int pmax)
   return (2 * maxsf + 3 * maxcell) * pmax * 3 + 2 * maxsf;
 }
 
+// A polytope's record of FINISHED tables in HBM (pdh_matfree.h: the matrix-free product reads them), at a fixed stride for the maxima
+// of the problem: the X tables [interior sub-face][axis] (FULLS stride, entry (k, l) at l * N1D + k, k the own index) | the D tables
+// [sub-face][axis] (packed symmetric, SYMS stride) | the M | K tables [cell][axis][M | K] (SYMS stride; reaction term folded into K of
+// axis 0).  The strides are Kind's (they depend on N1D alone).
+PDH_HD constexpr int matfree_off_d(int n1d, int maxsi) { return maxsi * 3 * ((n1d * n1d) | 1); }
+PDH_HD constexpr int matfree_off_c(int n1d, int maxsf, int maxsi)
+{
+  return matfree_off_d(n1d, maxsi) + maxsf * 3 * ((n1d * (n1d + 1) / 2) | 1);
+}
+PDH_HD constexpr int matfree_rec_doubles(int n1d, int maxsf, int maxsi, int maxcell)
+{
+  return matfree_off_c(n1d, maxsf, maxsi) + maxcell * 6 * ((n1d * (n1d + 1) / 2) | 1);
+}
+
 // the kinds of the wave-per-polytope kernel (pdh_terms.h) that are instantiated: f(N1D, BASIS) as integral constants; false: none
 template <class F>
 bool for_kind(int n1d, int basis, F &&f)

@@ -122,16 +122,30 @@ class MultigridHierarchy:
         self.contexts = []
 
 
-def _setup_level(ctx, l, inner, degree, smoother_precision):
-    """the solver of level 0, the smoother of every level above: what its set-up reported"""
-    info = ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree)
+def _setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator="stored", sip_values=True):
+    """the solver of level 0, the smoother of every level above: what its set-up reported, and under 'smoother_operator' which operator
+    the level's smoother applies.  'matrix_free' is taken where the context grants the tables (PDH_EUNSUPPORTED: the level stays
+    'stored') and its values are the SIP assembly of its own description (sip_values)."""
+    from ._capi import PDH_EUNSUPPORTED, PdhError
+
+    info = dict(ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree))
     if l > 0 and smoother_precision == "f32":
         ctx.set_smoother_precision("f32")
+    info["smoother_operator"] = "stored"
+    if l > 0 and smoother_operator == "matrix_free" and sip_values:
+        try:
+            info["matrix_free"] = ctx.setup_matrix_free()
+        except PdhError as e:
+            if e.code != PDH_EUNSUPPORTED:
+                raise
+        else:
+            ctx.set_smoother_operator("matrix_free")
+            info["smoother_operator"] = "matrix_free"
     return info
 
 
 def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = None, diag_first=True, degree=3, inner=None, device=0,
-                        smoother_precision="f64", coarse_operators="assembled"):
+                        smoother_precision="f64", coarse_operators="assembled", smoother_operator="stored"):
     """The reference's agglomerated multigrid (examples/simplex_agglomerated_multigrid.cc:378-515) on one device: one context per level
     handler of `levels` (coarse to fine, e.g. block_hierarchy's), each assembled like assemble_levels does (the Cartesian description
     where it is taken); Chebyshev of `degree` over `inner` ('block_jacobi' up to 64 dofs per polytope, 'jacobi' above, unless given) as
@@ -141,7 +155,10 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
     coarse_operators 'galerkin': only the finest level is assembled, every level below it gets A_(l-1) = P^T A_l P from the level above
     (Transfer.galerkin_device, the reference's AmgProjector::compute_level_matrices, include/multigrid_amg.h:267-305), fine to coarse,
     before any level is set up; at most 64 dofs per polytope.  'assembled' (default): every level assembles the SIP operator on its own
-    polytopes.  Returns a MultigridHierarchy; close() it."""
+    polytopes.  smoother_operator 'matrix_free': every level above the coarsest whose context grants the tables (Context.setup_matrix_free)
+    and whose values are the SIP assembly of its own polytopes - under 'galerkin' the finest only - takes the products of its smoother
+    and its residual from them (Context.set_smoother_operator); the other levels stay 'stored'.  info[l]["smoother_operator"] says which
+    is in force.  Returns a MultigridHierarchy; close() it."""
     from ._capi import Context, Multigrid, PdhError
     from .handler import HostError
 
@@ -152,6 +169,8 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
         raise ValueError("smoother_precision must be 'f64' or 'f32'")
     if coarse_operators not in ("assembled", "galerkin"):
         raise ValueError("coarse_operators must be 'assembled' or 'galerkin'")
+    if smoother_operator not in ("stored", "matrix_free"):
+        raise ValueError("smoother_operator must be 'stored' or 'matrix_free'")
     galerkin = coarse_operators == "galerkin"
     contexts, transfers, info, mg = [], [], [], None
     try:
@@ -172,14 +191,15 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
                 ctx.set_problem(flat)
             if not galerkin:
                 ctx.assemble_device()
-                info.append(_setup_level(ctx, l, inner, degree, smoother_precision))
+                info.append(_setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator))
             if l > 0:
                 transfers.append(level_transfer(ctx, levels[l - 1], ah))
         if galerkin:
             contexts[-1].assemble_device()
             for l in range(len(levels) - 1, 0, -1):
                 transfers[l - 1].galerkin_device(contexts[l - 1])
-            info = [_setup_level(ctx, l, inner, degree, smoother_precision) for l, ctx in enumerate(contexts)]
+            info = [_setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator, l == len(contexts) - 1)
+                    for l, ctx in enumerate(contexts)]
         mg = Multigrid(contexts, transfers)
     except Exception:
         MultigridHierarchy(contexts, transfers, mg, info).close()

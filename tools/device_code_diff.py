@@ -21,7 +21,7 @@ CSRC = os.path.join("polydeal_amd", "csrc")
 # (name, source, extra flags) of every device unit.  This list must match the .hip units of polydeal_amd/csrc/Makefile (pdh_inst.hip once per
 # PDH_GROUP): a unit that is missing here is a unit whose kernels the comparison does not see.
 UNITS = [("inst_g%d" % g, "pdh_inst.hip", ["-DPDH_GROUP=%d" % g]) for g in range(8)] + [
-    (u, "pdh_%s.hip" % u, []) for u in ("rhs", "eval", "exchange", "moment", "terms", "cartgen", "tiled", "solve", "shadow", "transfer")]
+    (u, "pdh_%s.hip" % u, []) for u in ("rhs", "eval", "exchange", "moment", "terms", "matfree", "cartgen", "tiled", "solve", "shadow", "transfer")]
 
 
 def makefile_flags(csrc):

@@ -41,6 +41,14 @@ bytes each must move (values, the gathered x, the index arrays, y); the shadow's
 set-up; one V-cycle with either precision; and the solve b = A x*, rel_tol 1e-13, F64 and F32 alternating, twice each.  Two conditions
 (fields f32_solve_faster_beyond_spread, f32_vmult_faster_beyond_spread): the F32 solve and the F32 product are faster than the F64 ones by
 more than the spread between the two F64 repeats.
+
+Matrix-free section (--vcycle --matrix-free, alone, combinable with --smoother-f32; pdh_setup_matrix_free, pdh_set_smoother_operator), written
+to profiles/r12_matrix_free.json unless --out says otherwise, on the hierarchy of the V-cycle section, ONE process, HIP events, medians of
+--reps, the stored path measured there being the yardstick: per level whether the tables are granted, their bytes and the wall time of
+the set-up; k_vmult, k_vmult_f32 and k_mf_vmult on the finest level, alternating twice each; one V-cycle and the solve b = A x*, rel_tol
+1e-13, with the stored and the matrix-free smoother operator alternating twice each (and once each over F32 inverses with
+--smoother-f32); the stored and the matrix-free product on FE_AggloDGP(3) and on grown agglomerates of the same cells.  Conditions (fields
+mf_faster_than_stored_beyond_spread, same_iterations_within_one, matrix_free_solve_not_slower); mf_faster_than_f32 is recorded either way.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -580,6 +588,168 @@ def smoother_f32_case(pa, torch, cells, reps, vcycle):
     return out
 
 
+def matrix_free_case(pa, torch, cells, reps, with_f32):
+    """the matrix-free smoother-operator figures: see the module docstring"""
+    from polydeal_amd._capi import Multigrid
+    from polydeal_amd.levels import block_hierarchy, multigrid_hierarchy
+
+    t0 = time.time()
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    fe = pa.FE_DGQ(3, 3)
+    n, degree = fe.n_dofs_per_cell, 3
+    stream = torch.cuda.current_stream().cuda_stream
+    handlers = block_hierarchy(grid, fe, [b for b in (32, 16, 8, 4, 2) if 2 * b <= cells])
+    hier = multigrid_hierarchy(handlers, fe, pa.SipVariant.poisson_example(fe), diag_first=True, degree=degree)
+    contexts, transfers, info = hier.contexts, hier.transfers, hier.info
+    state = {"mg": hier.mg}
+    hier.mg = None
+    N = handlers[-1].n_dofs
+    for c in contexts:
+        c.set_stream(stream)
+    fin = contexts[-1]
+    est = [i.get("estimate") for i in info]
+    stats = [c.stats() for c in contexts]
+    smooth = list(range(1, len(contexts)))
+    out = {"element": "FE_DGQ(3)", "cells_per_axis": cells, "preconditioner": "V-cycle", "smoother_degree": degree,
+           "rows": [c.n_rows for c in contexts], "n_values_finest": stats[-1]["n_values"], "levels": []}
+
+    def remake(mode):
+        """every smoother level set up again with its own estimate, then the mode: operator and precision; the V-cycle attached again"""
+        if state["mg"] is not None:
+            state["mg"].close()
+            state["mg"] = None
+        for l in smooth:
+            contexts[l].setup_chebyshev("block_jacobi", degree=degree, max_eigenvalue=est[l])
+            if mode.endswith("f32"):
+                contexts[l].set_smoother_precision("f32")
+            if mode.startswith("matrix_free") and granted[l]:
+                contexts[l].set_smoother_operator("matrix_free")
+        state["mg"] = Multigrid(contexts, transfers)
+    try:
+        # the tables: which levels are granted, their bytes, the wall time of the set-up (it synchronises)
+        granted = [False] * len(contexts)
+        for l in smooth:
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            try:
+                mf = contexts[l].setup_matrix_free()
+                granted[l] = True
+            except pa.PdhError as e:
+                if e.code != pa._capi.PDH_EUNSUPPORTED:
+                    raise
+                mf = {"refused": str(e)}
+            torch.cuda.synchronize()
+            out["levels"].append(dict(mf, level=l, rows=contexts[l].n_rows, values_bytes=8.0 * stats[l]["n_values"],
+                                      setup_matrix_free_wall_ms=(time.perf_counter() - w0) * 1e3))
+        out["granted_levels"] = [l for l in smooth if granted[l]]
+        # the three products on the finest level, alternating, twice each (F32 is in force for the shadow's product only)
+        if state["mg"] is not None:
+            state["mg"].close()
+            state["mg"] = None
+        fin.setup_chebyshev("block_jacobi", degree=degree, max_eigenvalue=est[-1])
+        fin.set_smoother_precision("f32")
+        x = torch.rand(N, dtype=torch.float64, device="cuda")
+        y = torch.empty(N, dtype=torch.float64, device="cuda")
+        prods = {"k_vmult": lambda: fin.vmult_device(x.data_ptr(), y.data_ptr()),
+                 "k_vmult_f32": lambda: fin.smoother_vmult_device(x.data_ptr(), y.data_ptr()),
+                 "k_mf_vmult": lambda: fin.matrix_free_vmult_device(x.data_ptr(), y.data_ptr())}
+        tm = {k: [] for k in prods}
+        for _ in range(2):
+            for k, fn in prods.items():
+                tm[k].append(event_times_ms(torch, fn, reps))
+        med = {k: [median(v) for v in tm[k]] for k in prods}
+        spread = max(abs(med[k][0] - med[k][1]) for k in ("k_vmult", "k_mf_vmult"))
+        tb = out["levels"][-1].get("table_bytes", 0)
+        out["products_finest"] = {
+            "ms_medians": med, "ms_min": {k: min(map(min, tm[k])) for k in prods}, "spread_ms": spread,
+            "bytes": {"k_vmult": vmult_bytes(stats[-1], n, N, False), "k_vmult_f32": vmult_bytes(stats[-1], n, N, True),
+                      "k_mf_vmult": tb + 8.0 * stats[-1]["n_values"] / n + 8.0 * N},
+            "mf_over_stored": median(med["k_mf_vmult"]) / median(med["k_vmult"]),
+            "mf_over_f32": median(med["k_mf_vmult"]) / median(med["k_vmult_f32"]),
+            "mf_faster_than_stored_beyond_spread": bool(min(med["k_vmult"]) - max(med["k_mf_vmult"]) > spread),
+            "mf_faster_than_f32": bool(max(med["k_mf_vmult"]) < min(med["k_vmult_f32"]))}
+        print(json.dumps(out["products_finest"]), flush=True)
+        # one V-cycle and the headline solve in every mode, stored and matrix-free alternating twice
+        modes = ["stored", "matrix_free", "stored", "matrix_free"] + (["stored+f32", "matrix_free+f32"] if with_f32 else [])
+        r, z = torch.rand(N, dtype=torch.float64, device="cuda"), torch.empty(N, dtype=torch.float64, device="cuda")
+        gen = torch.Generator(device="cuda").manual_seed(1)
+        xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=gen)
+        rhs = torch.empty(N, dtype=torch.float64, device="cuda")
+        fin.vmult_device(xs.data_ptr(), rhs.data_ptr())
+        out["solves"] = []
+        for mode in modes:
+            remake(mode)
+            ap = event_times_ms(torch, lambda: fin.precondition_device(r.data_ptr(), z.data_ptr()), reps)
+            sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            si = fin.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+            wall = time.perf_counter() - w0
+            its = si["iterations"]
+            res = torch.empty(N, dtype=torch.float64, device="cuda")
+            fin.residual_device(rhs.data_ptr(), sol.data_ptr(), res.data_ptr())
+            kind = "k_mf_vmult" if mode.startswith("matrix_free") else ("k_vmult_f32" if mode.endswith("f32") else "k_vmult")
+            out["solves"].append({"mode": mode, "vcycle_ms_median": median(ap), "vcycle_ms_min": min(ap), "iterations": its,
+                                  "products_finest": {"k_vmult (CG)": 1 + its, kind + " (smoother, residual)": (its + 1) * 2 * degree},
+                                  "wall_s": wall, "residual": si["residual"],
+                                  "true_relative_residual": float(torch.linalg.norm(res) / torch.linalg.norm(rhs)),
+                                  "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))})
+            print(json.dumps(out["solves"][-1]), flush=True)
+        ws = [s_["wall_s"] for s_ in out["solves"] if s_["mode"] == "stored"]
+        wm = [s_["wall_s"] for s_ in out["solves"] if s_["mode"] == "matrix_free"]
+        its_s = [s_["iterations"] for s_ in out["solves"] if s_["mode"] == "stored"]
+        its_m = [s_["iterations"] for s_ in out["solves"] if s_["mode"] == "matrix_free"]
+        out.update(solve_stored_wall_s=ws, solve_matrix_free_wall_s=wm, solve_stored_spread_s=abs(ws[0] - ws[1]),
+                   solve_matrix_free_speedup=median(ws) / median(wm),
+                   same_iterations_within_one=bool(abs(its_s[0] - its_m[0]) <= 1 and abs(its_s[1] - its_m[1]) <= 1),
+                   matrix_free_solve_not_slower=bool(median(wm) <= median(ws)))
+    finally:
+        if state["mg"] is not None:
+            state["mg"].close()
+        for t_ in transfers:
+            t_.close()
+        for c in contexts:
+            c.close()
+    # the same products on FE_AggloDGP(3) and on grown agglomerates of the bench cells (FE_DGQ(3)), a context each
+    out["other_products"] = []
+    for name in ("FE_AggloDGP(3), polytopes of 2^3", "FE_DGQ(3), grown agglomerates of 8 cells"):
+        if name.startswith("FE_AggloDGP"):
+            ah, fe2 = handler(pa, cells, "dgp")
+        else:
+            fe2 = pa.FE_DGQ(3, 3)
+            ah = pa.AgglomerationHandler(grid)
+            ah.define_grown_agglomerates(8, seed=cells)
+            ah.initialize_fe_values(4, 4)
+            ah.distribute_agglomerated_dofs(fe2)
+        ctx = pa.Context(0)
+        try:
+            ctx.set_stream(stream)
+            ctx.set_problem(ah.flatten(pa.SipVariant.poisson_example(fe2), True, False))
+            rec = {"what": name, "rows": ah.n_dofs, "polytopes": ah.n_agglomerates, "rows_kernel": ctx.rows_kernel_in_use()}
+            try:
+                rec.update(ctx.setup_matrix_free())
+            except pa.PdhError as e:
+                if e.code != pa._capi.PDH_EUNSUPPORTED:
+                    raise
+                rec["refused"] = str(e)
+            else:
+                ctx.assemble_device()
+                x = torch.rand(ah.n_dofs, dtype=torch.float64, device="cuda")
+                y = torch.empty(ah.n_dofs, dtype=torch.float64, device="cuda")
+                st = ctx.stats()
+                a, b = [], []
+                for _ in range(2):
+                    a.append(median(event_times_ms(torch, lambda: ctx.vmult_device(x.data_ptr(), y.data_ptr()), reps)))
+                    b.append(median(event_times_ms(torch, lambda: ctx.matrix_free_vmult_device(x.data_ptr(), y.data_ptr()), reps)))
+                rec.update(values_bytes=8.0 * st["n_values"], k_vmult_ms_medians=a, k_mf_vmult_ms_medians=b, mf_over_stored=median(b) / median(a))
+            out["other_products"].append(rec)
+            print(json.dumps(rec), flush=True)
+        finally:
+            ctx.close()
+    out["case_wall_s"] = time.time() - t0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
@@ -590,6 +760,9 @@ def main():
     ap.add_argument("--vcycle", action="store_true", help="the V-cycle section alone (default --out: profiles/r09_vcycle.json)")
     ap.add_argument("--smoother-f32", action="store_true",
                     help="with --vcycle or --chebyshev: the single-precision smoother section alone (--vcycle: default --out profiles/r10_smoother_f32.json)")
+    ap.add_argument("--matrix-free", action="store_true",
+                    help="with --vcycle: the matrix-free smoother-operator section alone, with --smoother-f32 also over F32 inverses "
+                         "(default --out: profiles/r12_matrix_free.json)")
     ap.add_argument("--galerkin", action="store_true",
                     help="with --vcycle: the Galerkin-product section alone (default --out: profiles/r11_galerkin.json)")
     ap.add_argument("--out", default=None)
@@ -597,6 +770,17 @@ def main():
     import torch
 
     import polydeal_amd as pa
+    if args.matrix_free:
+        if not args.vcycle or args.galerkin:
+            ap.error("--matrix-free goes with --vcycle (and --smoother-f32)")
+        out = {"tool": "tools/solve_bench.py --vcycle --matrix-free" + (" --smoother-f32" if args.smoother_f32 else ""),
+               "version": pa.load_library().pdh_version().decode(), "device": torch.cuda.get_device_name(0)}
+        out.update(matrix_free_case(pa, torch, args.cells, args.reps, args.smoother_f32))
+        doc = json.dumps(out, indent=1)
+        with open(args.out or os.path.join(ROOT, "profiles", "r12_matrix_free.json"), "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     if args.galerkin:
         if not args.vcycle or args.smoother_f32:
             ap.error("--galerkin goes with --vcycle alone")
