@@ -417,7 +417,7 @@ static int upload_rows_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &pl
 }
 
 // Term kernels: their tables, the records of 1-D rules the kernels read (gathered on the device from the point arrays), the
-// stamps of -DPDHT_STAMP builds
+// stamps of -DPDHT_STAMP builds, the work counter of pdh_terms_wg.h
 static int upload_terms_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &plan)
 {
   const TermsHost &TH = plan.terms;
@@ -445,6 +445,8 @@ static int upload_terms_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &p
   const size_t n_stamps = (size_t)std::max(K.n_owned, 1) * 16;
   PDH_TRY(device_buffer(ctx, n_stamps, &T.stamps, "term kernel: stamps"));
   PDH_HIP(ctx, hipMemset(T.stamps, 0, n_stamps * sizeof(long long)));
+  PDH_TRY(device_buffer(ctx, 16, &T.sched, "term kernel: work counter"));
+  PDH_HIP(ctx, hipMemset(T.sched, 0, 16 * sizeof(unsigned int)));
   ctx->prob.terms_merge[0] = TH.n_cells_in, ctx->prob.terms_merge[1] = TH.n_cells_out;
   ctx->prob.terms_merge[2] = TH.n_sf_in, ctx->prob.terms_merge[3] = TH.n_sf_out;
   return PDH_OK;
@@ -452,8 +454,10 @@ static int upload_terms_state(pdh_ctx *ctx, const Packed &K, const KernelPlan &p
 
 // Every launch pdh_set_algorithm can ask of the resident problem (pdh_ctx::Problem::direct / moment / row), resolved by the units that
 // instantiate the kernels
-static void resolve_launches(pdh_ctx *ctx, const Packed &K, const PlanSwitches &sw, int cus)
+// (why_row: set where the row kernel the plan chose could not be resolved - the set-up fails with it)
+static void resolve_launches(pdh_ctx *ctx, const Packed &K, const PlanSwitches &sw, int cus, const char **why_row)
 {
+  *why_row = nullptr;
   pdh_ctx::Problem &pr = ctx->prob;
   const PdhDev &D = pr.dev;
   const bool reaction = D.reaction_c != 0.0;
@@ -466,7 +470,12 @@ static void resolve_launches(pdh_ctx *ctx, const Packed &K, const PlanSwitches &
   if (pr.row_kernel == RowKernel::rows)
     pr.row = pdh_resolve_rows(&D, &pr.rows, pr.n_owned, cus, sw.rows_waves_per_cu, sw.rows_lds_pad, sw.rows_verbose, &pr.row_zero_sched);
   else if (pr.row_kernel == RowKernel::terms)
-    pr.row = pdh_resolve_terms(&D, &pr.terms, pr.n_owned, sw.terms_wg_waves);
+    {
+      const char *why = nullptr;
+      pr.row = pdh_resolve_terms(&D, &pr.terms, pr.n_owned, cus, sw.terms_wg_waves, sw.terms_wg_batch, &why);
+      if (!pr.row.kernel)
+        *why_row = why;
+    }
 }
 
 static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begin, int32_t row_end, const pdh_cartesian_points *cart);
@@ -546,7 +555,10 @@ static int set_problem_impl(pdh_ctx *ctx, const pdh_problem *p, int32_t row_begi
   ctx->prob.row_kernel = plan->kernel;
   ctx->prob.why_terms = plan->why_terms;
   // 4. the launches of every form of the problem
-  resolve_launches(ctx, K, sw, cus);
+  const char *why_row = nullptr;
+  resolve_launches(ctx, K, sw, cus, &why_row);
+  if (why_row) // (a launch that could not be resolved would answer a bare hipErrorInvalidValue at the first assembly)
+    return fail(ctx, PDH_EUNSUPPORTED, std::string("the row kernel chosen for this problem cannot be launched on this device: ") + why_row);
   ctx->prob.resident = true;
   ctx->ev_used = 0;
   guard.done = true;
@@ -626,6 +638,7 @@ extern "C" int pdh_assemble_device(pdh_ctx *ctx)
           PDH_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
         }
       if (pr.row_kernel == RowKernel::terms)
+        // (always on the context's stream: the launches of a problem share its work counter, pdh_terms_wg.h)
         PDH_HIP(ctx, pdh_launch_terms(&pr.row, &pr.dev, &pr.terms, pr.n_owned, ctx->stream));
       else
         PDH_HIP(ctx, pdh_launch_rows(&pr.row, pr.row_zero_sched, &pr.dev, &pr.rows, pr.d_mtab, pr.n_owned, ctx->stream));
@@ -869,7 +882,7 @@ extern "C" int pdh_values_checksum(pdh_ctx *ctx, double *out4)
   if (!out4)
     return fail(ctx, PDH_EINVAL, "out4 is NULL");
   PDH_HIP(ctx, hipSetDevice(ctx->device));
-  double *d = ctx->checksum.get<double>(4);
+  double *d = ctx->checksum.get<double>(pdh_checksum_doubles());
   if (!d)
     return fail(ctx, PDH_EDEVICE, "pdh_values_checksum: out of device memory");
   hipError_t e = pdh_launch_checksum(ctx->prob.dev.values, ctx->prob.n_values, d, ctx->stream);

@@ -108,7 +108,7 @@ struct pdh_ctx
   } io;
   int shape_key = -1; // cached multi-index table of pdh_shape_values (per dim / degree / basis)
   DevBuf shape_midx;
-  DevBuf checksum;          // the four doubles of pdh_values_checksum
+  DevBuf checksum;          // the four doubles of pdh_values_checksum, then its workgroups' partials
   double *pinned = nullptr; // [PDH_CG_NSCALARS] the word the CG loop reads its residual through
 
   // ---- what lives as long as the resident problem: free_problem() assigns a fresh one ----

@@ -60,7 +60,48 @@ extern "C" hipError_t pdh_launch_ghost_apply(const PdhDev *P, const double *recv
 // Validity signal for matrices too large to copy back (pdh_values_checksum): sum, sum of |.|, max |.| and the number of
 // non-finite entries of the owned rows' values, in one pass over HBM.  For FE_DGQ the sum of all entries is 1^T A 1, which
 // the SIP form fixes in closed form (sigma |dOmega| + c |Omega| for Nitsche boundaries) - bench.py checks it every run.
+// The sums are formed in a FIXED order - per thread, per wave (shuffles), per workgroup (its waves in order), then the workgroups'
+// partials by one workgroup in the same way - so two calls on the same values answer the same bits, whatever else runs on the device
+// (with one atomic add per wave into the result the last bit followed the order in which the waves arrived).
 // ---------------------------------------------------------------------------------------------------------------------
+constexpr int CHECKSUM_BLOCKS = 2048;
+// sum | sum of |.| | max |.| | non-finite count of the calling workgroup's 256 threads -> o[0 .. 3] (thread 0 writes)
+__device__ __forceinline__ void checksum_block_reduce(double s, double sa, double mx, double bad, double *__restrict__ o)
+{
+  __shared__ double part[4][4];
+  for (int d = 32; d > 0; d >>= 1)
+    {
+      s += __shfl_down(s, d);
+      sa += __shfl_down(sa, d);
+      bad += __shfl_down(bad, d);
+      mx = fmax(mx, __shfl_down(mx, d));
+    }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+    part[w][0] = s, part[w][1] = sa, part[w][2] = mx, part[w][3] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    {
+      o[0] = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
+      o[1] = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
+      o[2] = fmax(fmax(part[0][2], part[1][2]), fmax(part[2][2], part[3][2]));
+      o[3] = (part[0][3] + part[1][3]) + (part[2][3] + part[3][3]);
+    }
+}
+// partials [CHECKSUM_BLOCKS][4] of k_checksum -> out[0 .. 3]; one workgroup
+__global__ void __launch_bounds__(256) k_checksum_final(const double *__restrict__ partials, double *__restrict__ out)
+{
+  double s = 0.0, sa = 0.0, mx = 0.0, bad = 0.0;
+  for (int b = threadIdx.x; b < CHECKSUM_BLOCKS; b += 256)
+    {
+      s += partials[4 * b + 0];
+      sa += partials[4 * b + 1];
+      mx = fmax(mx, partials[4 * b + 2]);
+      bad += partials[4 * b + 3];
+    }
+  checksum_block_reduce(s, sa, mx, bad, out);
+}
+// out: partials [gridDim.x][4]
 __global__ void __launch_bounds__(256) k_checksum(const double *__restrict__ v, const int64_t n, double *__restrict__ out)
 {
   double s = 0.0, sa = 0.0, mx = 0.0, bad = 0.0;
@@ -76,29 +117,17 @@ __global__ void __launch_bounds__(256) k_checksum(const double *__restrict__ v, 
       else
         bad += 1.0;
     }
-  for (int o = 32; o > 0; o >>= 1)
-    {
-      s += __shfl_down(s, o);
-      sa += __shfl_down(sa, o);
-      bad += __shfl_down(bad, o);
-      mx = fmax(mx, __shfl_down(mx, o));
-    }
-  if ((threadIdx.x & 63) == 0)
-    {
-      atomicAdd(out + 0, s);
-      atomicAdd(out + 1, sa);
-      atomicAdd(out + 3, bad);
-      // max through the integer order of non-negative doubles
-      atomicMax(reinterpret_cast<unsigned long long *>(out + 2), (unsigned long long)__double_as_longlong(mx));
-    }
+  checksum_block_reduce(s, sa, mx, bad, out + 4 * blockIdx.x);
 }
 
-extern "C" hipError_t pdh_launch_checksum(const double *values, int64_t n, double *d_out4, hipStream_t stream)
+extern "C" size_t pdh_checksum_doubles() { return 4 + 4 * (size_t)CHECKSUM_BLOCKS; }
+extern "C" hipError_t pdh_launch_checksum(const double *values, int64_t n, double *d_out, hipStream_t stream)
 {
-  hipError_t e = hipMemsetAsync(d_out4, 0, 4 * sizeof(double), stream);
+  hipError_t e = hipMemsetAsync(d_out, 0, 4 * sizeof(double), stream);
   if (e != hipSuccess || n <= 0)
     return e;
-  hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, stream, values, n, d_out4);
+  hipLaunchKernelGGL(k_checksum, dim3(CHECKSUM_BLOCKS), dim3(256), 0, stream, values, n, d_out + 4);
+  hipLaunchKernelGGL(k_checksum_final, dim3(1), dim3(256), 0, stream, d_out + 4, d_out);
   return hipGetLastError();
 }
 

@@ -99,8 +99,10 @@ PdhLaunch pdh_resolve_rows(const PdhDev *P, const PdhRows *R, int count, int cus
 hipError_t pdh_launch_rows(const PdhLaunch *L, bool zero_sched, const PdhDev *P, const PdhRows *R, const double *mtab, int count,
                            hipStream_t stream);
 
-// pdh_terms.hip; wg_waves: waves of a workgroup of the FE_DGQ(3) kernel, 4 | 8
-PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int wg_waves);
+// pdh_terms.hip; FE_DGQ(3) kernel: wg_waves: writer waves of a workgroup, 4 | 8; its grid is min(count, cus), or, wg_batch > 0,
+// ceil(count / wg_batch) workgroups (PlanSwitches).  Nothing is resolved (kernel NULL) where that kernel would not be alone on its CU:
+// *why (never NULL) names the reason, and set-up fails with it.  Launches of one problem share its work counter: one stream, in order
+PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int cus, int wg_waves, int wg_batch, const char **why);
 hipError_t pdh_launch_terms(const PdhLaunch *L, const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream);
 hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T, double *out, int count, hipStream_t stream);
 
@@ -130,7 +132,9 @@ hipError_t pdh_launch_pack_faces(int dim, int64_t nqf, const double *fq_x, const
 hipError_t pdh_launch_ghost_apply(const PdhDev *P, const double *recv, int n_r21, const int64_t *r21_src, const int64_t *r21_dst,
                                   const int32_t *r21_rlen, int n_r22, const int64_t *r22_ptr, const int64_t *r22_src,
                                   const int32_t *r22_slot, hipStream_t stream);
-hipError_t pdh_launch_checksum(const double *values, int64_t n, double *d_out4, hipStream_t stream);
+// d_out [pdh_checksum_doubles()]: the four results, then scratch for the workgroups' partials (summed in a fixed order: reproducible bits)
+size_t pdh_checksum_doubles();
+hipError_t pdh_launch_checksum(const double *values, int64_t n, double *d_out, hipStream_t stream);
 
 // pdh_solve.hip
 // y[own rows] = A x (x in the global dof numbering).  part (may be NULL): per slot, sum_i y_i x_i over the slot's own rows.

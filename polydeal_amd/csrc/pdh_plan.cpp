@@ -1553,7 +1553,8 @@ PlanSwitches read_plan_switches()
   s.terms_dgq3_off = first("PDH_TERMS_DGQ3") == '0';
   s.rows_waves_per_cu = getenv("PDH_ROWS_WAVES_PER_CU") ? atoi(getenv("PDH_ROWS_WAVES_PER_CU")) : 0;
   s.rows_lds_pad = getenv("PDH_ROWS_LDS_PAD") ? (size_t)atol(getenv("PDH_ROWS_LDS_PAD")) : 0;
-  s.terms_wg_waves = getenv("PDH_TERMS_WG_WAVES") && atoi(getenv("PDH_TERMS_WG_WAVES")) == 8 ? 8 : 4;
+  s.terms_wg_waves = getenv("PDH_TERMS_WG_WAVES") && atoi(getenv("PDH_TERMS_WG_WAVES")) == 4 ? 4 : 8;
+  s.terms_wg_batch = getenv("PDH_TERMS_WG_BATCH") ? atoi(getenv("PDH_TERMS_WG_BATCH")) : 0;
   return s;
 }
 

@@ -176,14 +176,15 @@ int pack_problem(std::string &err, const pdh_problem *p, int32_t row_begin, int3
 
 // The diagnostic switches of the library: PDH_TERMS_MERGE (0, 2, else 1), PDH_TERMS_SPLIT (0 / 1, unset: -1), PDH_TRACE_SETUP,
 // PDH_ROWS_VERBOSE, PDH_TERMS=0, PDH_TERMS_DGQ3=0 for the planner; PDH_ROWS_WAVES_PER_CU (> 0: resident waves per CU of the row kernel),
-// PDH_ROWS_LDS_PAD (bytes) and PDH_TERMS_WG_WAVES (8, else 4) for the resolvers of the launches (pdh_launch.h).  read_plan_switches is
+// PDH_ROWS_LDS_PAD (bytes), PDH_TERMS_WG_WAVES (writer waves: 4, else 8) and PDH_TERMS_WG_BATCH (N > 0: ceil(n_owned / N) workgroups, so that
+// small problems reach workgroups of several polytopes) for the resolvers of the launches (pdh_launch.h).  read_plan_switches is
 // the library's only reader of the environment but for PDH_HOST_THREADS above; pdh_set_problem* and pdh_check_* call it on every call, so
 // every switch takes effect at the next set-up and holds for that resident problem (the tests compare the kernels in one process).
 struct PlanSwitches
 {
   int terms_merge = 1, terms_split = -1;
   bool trace = false, rows_verbose = false, terms_off = false, terms_dgq3_off = false;
-  int rows_waves_per_cu = 0, terms_wg_waves = 4;
+  int rows_waves_per_cu = 0, terms_wg_waves = 8, terms_wg_batch = 0;
   size_t rows_lds_pad = 0;
 };
 PlanSwitches read_plan_switches();

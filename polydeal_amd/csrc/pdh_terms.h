@@ -240,6 +240,48 @@ struct TermTasks
     });
     return r;
   }
+  // The loads of a lane task ALONE, for a caller that requests the data of a polytope before it may wait for them (the builder waves of
+  // pdh_terms_wg.h, a polytope ahead): g = the task's piece of the record, whose address depends on the slot alone; nothing here looks
+  // at a loaded value.  npts, ws0 and wc0 are left 0: tang_npts / cell_npts and task_first_weights give them once the data have arrived.
+  // CROSS: the side-1 weights too (tangential tasks)
+  template <bool CROSS>
+  __device__ __forceinline__ static Pts task_request(const double *g, int half)
+  {
+    Pts r;
+    r.npts = 0;
+    r.ws0 = r.wc0 = 0.0;
+    const double *gh = g + (PAIR ? PMAX * half : 0);
+    static_for<0, PMAX>([&](auto i_) {
+      constexpr int i = i_;
+      r.x[i] = gh[i];
+      r.ws[i] = gh[TPM + i];
+      r.wc[i] = CROSS ? gh[2 * TPM + i] : 0.0;
+    });
+    return r;
+  }
+  // ws0, wc0 (the weights of the task's first point, what tang_load / cell_load read from g[TPM], g[2 TPM]) from the data of the request: the
+  // lane's own first slot, PAIR: that of the even lane of its pair (call with both lanes of every pair active)
+  __device__ __forceinline__ static void task_first_weights(Pts &r)
+  {
+    auto even = [](double v) {
+      const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0xA0 /* quad_perm [0,0,2,2] */, 0xf, 0xf, true);
+      const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0xA0, 0xf, 0xf, true);
+      return __hiloint2double(hi, lo);
+    };
+    r.ws0 = PAIR ? even(r.ws[0]) : r.ws[0];
+    r.wc0 = PAIR ? even(r.wc[0]) : r.wc[0];
+  }
+  __device__ __forceinline__ static int tang_npts(int info, int dir, int fn, int half)
+  { // (as in tang_load)
+    const int npts = ((info >> (dir ? 15 : 12)) & 7) * fn;
+    return PAIR ? (npts - PMAX * half < 0 ? 0 : (npts - PMAX * half > PMAX ? PMAX : npts - PMAX * half)) : npts;
+  }
+  __device__ __forceinline__ static int cell_npts(const Pts &r)
+  { // (as in cell_load: slots behind the last interval carry zero weights)
+    int n = 0;
+    static_for<0, PMAX>([&](auto i_) { n += r.ws[i_] != 0.0 ? 1 : 0; });
+    return n;
+  }
   __device__ __forceinline__ void cell_compute(const CPts &r, int ct, int half = 0) const
   {
     const int cell = ct / 3, d = ct - 3 * cell;

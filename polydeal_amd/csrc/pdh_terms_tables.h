@@ -41,6 +41,7 @@ struct PdhTerms
   int32_t lds_bytes;      // dynamic LDS of a workgroup for these maxima
   int32_t split;          // 1: X tables made in a second pass over the D tables (pdh_terms.h: SPLIT) - lds_bytes is that form's
   long long *stamps;      // [n_owned][16] cycle counter at the phase boundaries; written by -DPDHT_STAMP builds only
+  unsigned int *sched;    // [2] pdh_terms_wg.h: work counter of its workgroups and count of those that have left (both zero between launches)
 };
 
 namespace pdht

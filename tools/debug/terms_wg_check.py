@@ -51,7 +51,7 @@ if mode in ("check", "both"):
         except AssertionError as e:
             ok, bad = False, bad + 1
             print("   ", str(e)[:300])
-        print("dgq3 %-5s n=%d per=%d %-7s diag_first=%d W=%s: %s err %.2e %s" % (kind, n, per, vname, diag_first, os.environ.get("PDH_TERMS_WG_WAVES", "4"),
+        print("dgq3 %-5s n=%d per=%d %-7s diag_first=%d W=%s: %s err %.2e %s" % (kind, n, per, vname, diag_first, os.environ.get("PDH_TERMS_WG_WAVES", "8"),
                                                                               used, err, "ok" if ok else "FAIL"), flush=True)
     print("failures:", bad)
 if mode in ("time", "both") and not bad:
@@ -81,5 +81,5 @@ if mode in ("time", "both") and not bad:
         ctx.close()
     a, b = res["1"], res["0"]
     print("dgq3 %s W=%s: terms_wg %.3f ms (min %.3f) %s | pdh_rows %.3f ms (min %.3f) %s | sums %.10e %.10e"
-          % ("grown" if grown else "block", os.environ.get("PDH_TERMS_WG_WAVES", "4"), a[0], a[1], a[2], b[0], b[1], b[2], a[3]["sum"], b[3]["sum"]), flush=True)
+          % ("grown" if grown else "block", os.environ.get("PDH_TERMS_WG_WAVES", "8"), a[0], a[1], a[2], b[0], b[1], b[2], a[3]["sum"], b[3]["sum"]), flush=True)
 sys.exit(1 if bad else 0)

@@ -150,6 +150,59 @@ __global__ void __launch_bounds__(64 * SHARE) k_rows_shared(double *v, unsigned 
       }
 }
 
+// The geometry of the batched k_terms_wg (pdh_terms_wg.h): workgroups of 8 writer waves + 4 waves that only keep the barriers (the
+// table builders there), one workgroup per CU (by its LDS), one barrier per polytope.
+// order 0: workgroup b takes the S consecutive polytopes [b S, (b + 1) S); 1: its k-th polytope is b + k gridDim.x (the CUs write one
+// dense window of regions that moves through the values); 2: polytopes handed out by the device-wide counter, fetched a step ahead by
+// the first idle wave (needs 768 threads) - the writers never wait for the counter.
+// drain 0: a writer goes to the barrier with its stores in flight; 1: every writer waits for its stores first (vmcnt(0)); 2: wave 0
+// alone does (what the atomic of k_rows_shared costs its wave 0: vmcnt retires in order)
+template <int AUX>
+__global__ void __launch_bounds__(768, 1) k_rows_team(double *v, unsigned *sched, int n_poly, int nb, int spin, int S, int order, int drain)
+{
+  extern __shared__ double lds[];
+  __shared__ int nxt[2];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int first = order == 0 ? (int)blockIdx.x * S : (int)blockIdx.x, step = order == 0 ? 1 : (int)gridDim.x;
+  const int last = order == 0 ? (first + S < n_poly ? first + S : n_poly) : n_poly;
+  double acc = lane;
+  const int rlen = nb * 64;
+  int slot = first;
+  for (int k = 0; slot < last; ++k)
+    {
+      if (order == 2 && threadIdx.x == 512)
+        nxt[k & 1] = (int)gridDim.x + (int)__hip_atomic_fetch_add(sched, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (w < 8)
+        {
+          for (int s = 0; s < spin; ++s)
+#pragma unroll
+            for (int k = 0; k < 64; ++k)
+              acc = acc * 1.0000001 + 1e-9;
+          const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(v + (size_t)slot * 64 * rlen, 0, 64 * rlen * 8, 0x00020000);
+          for (int b = 0; b < nb; ++b)
+            {
+              unsigned off = 64u * 8u * (unsigned)b + (unsigned)(w * 8) * (unsigned)rlen * 8u;
+#pragma unroll
+              for (int r = 0; r < 8; ++r)
+                {
+                  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, acc + r), rs, lane * 8, off, AUX);
+                  off += (unsigned)rlen * 8u;
+                }
+            }
+          if (drain == 1 || (drain == 2 && w == 0))
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+      __syncthreads();
+      slot = order == 2 ? nxt[k & 1] : slot + step;
+    }
+  if (order == 2 && threadIdx.x == 0)
+    if (__hip_atomic_fetch_add(sched + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1)
+      {
+        __hip_atomic_store(sched, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(sched + 1, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      }
+}
+
 // The store pattern a workgroup-of-eight row kernel would have: a workgroup takes EIGHT polytopes at a time (wave w computes
 // polytope 8 s + w); the six coupling blocks are written in six phases - in phase b every wave writes its eight rows
 // (8 w .. 8 w + 7) of piece b of all eight polytopes, barrier - and each wave writes the 64 rows of the own block (piece 6 here)
@@ -292,6 +345,47 @@ int main()
     std::printf("aux 18  %d waves share a polytope  spin %2d  %2d waves/CU = %d workgroups/CU = %d concurrent regions: %.3f ms  %.2f TB/s\n", SHARE,
                 spin, waves_per_cu, wg_per_cu, grid, ms, n * 8.0 / ms / 1e9);
   };
+  // the batched k_terms_wg's geometry against the two shapes it is compared with, three repeats of each (the spread is the yardstick)
+  auto run_team = [&](auto aux_, int spin, int S, int order = 0, int drain = 0, int threads = 768) {
+    constexpr int AUX = decltype(aux_)::value;
+    const size_t lds = 96 * 1024; // more than half of a CU's 160 KB: one workgroup per CU
+    CHECK(hipFuncSetAttribute((const void *)k_rows_team<AUX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int per_cu = 0;
+    CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_rows_team<AUX>, threads, lds));
+    const int grid = (NP + S - 1) / S;
+    auto launch = [&] { hipLaunchKernelGGL(k_rows_team<AUX>, dim3(grid), dim3(threads), lds, 0, v, sched, NP, NB, spin, S, order, drain); };
+    launch();
+    CHECK(hipDeviceSynchronize());
+    CHECK(hipEventRecord(e0));
+    for (int i = 0; i < 5; ++i)
+      launch();
+    CHECK(hipEventRecord(e1));
+    CHECK(hipDeviceSynchronize());
+    float ms;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    ms /= 5;
+    std::printf("aux %2d  team: 8 writer + %d idle waves, %d workgroup/CU, batches of %3d %s, %s, grid %5d  spin %2d: %.3f ms  %.2f TB/s\n", AUX,
+                threads / 64 - 8, per_cu, S, order == 2 ? "by counter " : (order ? "interleaved" : "consecutive"),
+                drain == 1 ? "writers drain their stores" : (drain ? "wave 0 drains its stores  " : "stores left in flight     "), grid, spin, ms, n * 8.0 / ms / 1e9);
+  };
+  for (int rep = 0; rep < 3; ++rep)
+    {
+      run_shared(std::integral_constant<int, 4>{}, 16, 16);
+      run_shared(std::integral_constant<int, 8>{}, 16, 8);
+      for (int order : {0, 1, 2})
+        for (int drain : {0, 1, 2})
+          run_team(std::integral_constant<int, 18>{}, 16, order == 2 ? 128 : 32, order, drain);
+      for (int order : {0, 2})
+        for (int drain : {0, 1})
+          run_team(std::integral_constant<int, 2>{}, 16, order == 2 ? 128 : 32, order, drain);
+    }
+  for (int S : {4, 8, 16, 128})
+    for (int drain : {0, 1})
+      run_team(std::integral_constant<int, 18>{}, 16, S, 0, drain);
+  for (int drain : {0, 1})
+    run_team(std::integral_constant<int, 18>{}, 16, 32, 0, drain, 512);
+  if (getenv("ROWS_PROBE_TEAM_ONLY"))
+    return 0;
   for (int per_cu : {8, 16})
     {
       run_shared(std::integral_constant<int, 1>{}, 16, per_cu);

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Phase timing of the workgroup-per-polytope kernel (pdh_terms_wg.h, W = 4) from in-kernel cycle-counter stamps
-(library built with -DPDHT_STAMP):  python tools/terms_wg_stamps.py build/tstamp/libpolydeal_hip.so [cells] [grown]"""
+"""Step timing of the FE_DGQ(3) workgroup kernel (pdh_terms_wg.h) from in-kernel cycle-counter stamps (library built with
+-DPDHT_STAMP):  python tools/terms_wg_stamps.py build/tstamp/libpolydeal_hip.so [cells] [grown]
+Per polytope: the first and the last writer wave (start of the step, last store issued, barrier left) and the first and the last
+builder wave (requests of the next polytope issued, tables of this one done, barrier left)."""
 import ctypes as C
 import os
 import sys
@@ -27,10 +29,14 @@ n = ctx.stats()["n_owned_agg"]
 out = np.zeros((n, 16), dtype=np.int64)
 ctx.lib.pdh_debug_rows_stamps.argtypes = [C.c_void_p, C.c_void_p]
 assert ctx.lib.pdh_debug_rows_stamps(ctx.h, out.ctypes.data) == 0
-st = out.reshape(n, 4, 4).astype(np.float64)
-life = st[:, :, 3] - st[:, :, 0]
-print("FE_DGQ(3) %s, W = 4: %d polytopes; mean lifetime of a wave %.0f cycles" % ("grown" if grown else "blocks", n, life.mean()))
-names = ["A: loads + lane tasks + barriers", "B: own block (terms of cells and sub-faces)", "B: pieces (coupling terms + all row stores)"]
-for k, nm in enumerate(names):
-    d = st[:, :, k + 1] - st[:, :, k]
-    print("%-48s mean %8.0f (%4.1f %%)   by wave: %s" % (nm, d.mean(), 100 * d.mean() / life.mean(), " ".join("%.0f" % d[:, w].mean() for w in range(4))))
+st = out[:, :12].reshape(n, 4, 3).astype(np.float64)
+print("FE_DGQ(3) %s, %d polytopes, writer waves %s" % ("grown" if grown else "blocks", n, os.environ.get("PDH_TERMS_WG_WAVES", "8")))
+for w, nm in ((0, "first writer"), (1, "last writer ")):
+    step, busy, wait = st[:, w, 2] - st[:, w, 0], st[:, w, 1] - st[:, w, 0], st[:, w, 2] - st[:, w, 1]
+    print("%s: step %8.0f cycles (median %8.0f) = tables to last store issued %8.0f + wait at the barrier %8.0f (%4.1f %% of a step)"
+          % (nm, step.mean(), np.median(step), busy.mean(), wait.mean(), 100 * wait.mean() / step.mean()))
+for w, nm in ((2, "first builder"), (3, "last builder ")):
+    ok = st[:, w, 0] > 0
+    busy, idle = (st[:, w, 1] - st[:, w, 0])[ok], (st[:, w, 2] - st[:, w, 1])[ok]
+    print("%s: requests issued to tables done %8.0f cycles (median %8.0f), idle at the barrier %8.0f (%4.1f %%)"
+          % (nm, busy.mean(), np.median(busy), idle.mean(), 100 * idle.mean() / (busy.mean() + idle.mean())))
