@@ -13,7 +13,11 @@
 // (pdh_setup_chebyshev: smoothing range 20, 20 CG steps for the eigenvalue estimate - the reference's multigrid smoother settings).
 // `--smoother-f32` after that lets the polynomial read a float32 copy of the matrix and of the block inverses
 // (pdh_set_smoother_precision); CG itself, every vector and every sum stay double.
-// Usage: poisson [--device-solve [--chebyshev <degree> [--smoother-f32]]] [path/to/t3.msh]
+// `--p-multigrid` after `--device-solve` preconditions the t3.msh solves of degree 2 .. 4 with a V-cycle over the degrees 1 .. p on the
+// SAME 364 grown agglomerates (pdh_ptransfer_create: FE_AggloDGP levels are connected by an index map; pdh_mg_create): Chebyshev(3) over
+// block Jacobi smooths every level, and the coarsest level (degree 1, 1092 rows - just above the cap of the dense solve) is one
+// application of it.  Degree 1 and the reference's FE_DGQ(1) case keep block Jacobi.
+// Usage: poisson [--device-solve [--chebyshev <degree> [--smoother-f32] | --p-multigrid]] [path/to/t3.msh]
 #include "../polydeal_amd/csrc/host/polydeal_host.h"
 #include "host_solver.h"
 
@@ -22,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 
 using namespace polydeal_hip;
 
@@ -42,6 +47,85 @@ int reference_case();             // test/polydeal/poisson.cc, solved on the dev
 
 int chebyshev_degree = 0; // --chebyshev: 0 = plain block Jacobi
 bool smoother_f32 = false; // --smoother-f32: the Chebyshev polynomial reads the float32 shadow
+
+bool p_multigrid = false; // --p-multigrid: V-cycle over the degrees 1 .. p on the same agglomerates
+
+// The levels below the finest of a p-hierarchy on the agglomerates of the example: one handler and one context per degree 1 .. p - 1,
+// assembled like the finest, the transfers between consecutive degrees and the mg that makes the V-cycle the preconditioner of `fine`.
+struct PHierarchy
+{
+  std::vector<std::unique_ptr<AgglomerationHandler>> handlers;
+  std::vector<pdh_ctx *> contexts; // coarse to fine, the last is the caller's
+  std::vector<pdh_transfer *> transfers;
+  pdh_mg *mg = nullptr;
+  ~PHierarchy()
+  {
+    pdh_mg_destroy(mg);
+    for (pdh_transfer *t : transfers)
+      pdh_transfer_destroy(t);
+    for (size_t l = 0; l + 1 < contexts.size(); ++l)
+      pdh_destroy(contexts[l]);
+  }
+  // false: the message is on stderr
+  bool build(const BackgroundGrid &tria, const AgglomerationHandler &fine_ah, pdh_ctx *fine, unsigned fe_degree)
+  {
+    const pdh_chebyshev_control cheb = {PDH_PREC_BLOCK_JACOBI, 3, 20.0, 20, 0.0};
+    const AgglomerationHandler *below = nullptr; // the level handled before: the coarse side of the pair
+    for (unsigned q = 1; q <= fe_degree; ++q)
+      {
+        const AgglomerationHandler *ah = &fine_ah;
+        pdh_ctx *ctx = fine;
+        if (q < fe_degree)
+          {
+            handlers.emplace_back(new AgglomerationHandler(tria));
+            partition_into_grown_agglomerates(*handlers.back(), 364, 364); // the same seed: the same polytopes
+            const FE_AggloDGP<2> fe(q);
+            handlers.back()->initialize_fe_values(q + 1, q + 1);
+            handlers.back()->distribute_agglomerated_dofs(fe);
+            ah = handlers.back().get();
+            FlatProblem F;
+            ah->flatten(SipVariant::poisson_example(fe), F, true, false);
+            ctx = nullptr;
+            if (pdh_create(&ctx, 0) != PDH_OK)
+              return std::fprintf(stderr, "%s\n", pdh_last_error(nullptr)), false;
+            contexts.push_back(ctx);
+            if (pdh_set_problem(ctx, &F.c) != PDH_OK || pdh_assemble_device(ctx) != PDH_OK)
+              return std::fprintf(stderr, "%s\n", pdh_last_error(ctx)), false;
+          }
+        else
+          contexts.push_back(ctx);
+        // (the coarsest level has 3 x 364 = 1092 rows, above the 1024 of pdh_setup_direct: one Chebyshev application is its "solve")
+        if (pdh_setup_chebyshev(ctx, &cheb, nullptr) != PDH_OK)
+          return std::fprintf(stderr, "%s\n", pdh_last_error(ctx)), false;
+        if (below)
+          {
+            const Utils::PTransferDescription T(*below, *ah);
+            pdh_transfer *t = nullptr;
+            if (pdh_ptransfer_create(ctx, &T.c, &t) != PDH_OK)
+              return std::fprintf(stderr, "%s\n", pdh_last_error(ctx)), false;
+            transfers.push_back(t);
+          }
+        below = ah;
+      }
+    if (pdh_mg_create((int)contexts.size(), contexts.data(), transfers.data(), &mg) != PDH_OK)
+      return std::fprintf(stderr, "%s\n", pdh_last_error(fine)), false;
+    return true;
+  }
+};
+
+// CG on the finest context of a p-hierarchy: the stop rule of device_solve, the V-cycle as the preconditioner
+int p_multigrid_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<double> &x)
+{
+  x.assign(rhs.size(), 0.0);
+  const pdh_cg_control control = {20000, 1e-13, 0.0};
+  pdh_cg_result res;
+  if (pdh_solve_cg(ctx, &control, rhs.data(), x.data(), &res) != PDH_OK)
+    {
+      std::fprintf(stderr, "%s\n", pdh_last_error(ctx));
+      return -1;
+    }
+  return res.iterations;
+}
 
 // preconditioned CG on the resident matrix: block Jacobi or Chebyshev over it, the stop rule of example_solver::solve_cg
 int device_solve(pdh_ctx *ctx, const std::vector<double> &rhs, std::vector<double> &x)
@@ -88,6 +172,17 @@ int main(int argc, char **argv)
               ++argv;
             }
         }
+      else if (argc > 1 && std::strcmp(argv[1], "--p-multigrid") == 0)
+        {
+          p_multigrid = true;
+          --argc;
+          ++argv;
+        }
+    }
+  if (argc > 1 && std::strcmp(argv[1], "--p-multigrid") == 0)
+    {
+      std::fprintf(stderr, "--p-multigrid is accepted only directly after --device-solve\n");
+      return 1;
     }
   if (argc > 1 && std::strcmp(argv[1], "--smoother-f32") == 0)
     {
@@ -165,10 +260,19 @@ int main(int argc, char **argv)
 
       // ---- solve()
       std::vector<double> solution;
-      const int its = on_device ? device_solve(ctx, rhs, solution) : example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
+      const bool v_cycle = p_multigrid && fe_degree >= 2;
+      int its = -1;
+      if (v_cycle)
+        {
+          PHierarchy hierarchy; // (the mg, the transfers and the coarse contexts go before ctx does)
+          if (hierarchy.build(tria, ah, ctx, fe_degree))
+            its = p_multigrid_solve(ctx, rhs, solution);
+        }
+      else
+        its = on_device ? device_solve(ctx, rhs, solution) : example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
       if (its < 0)
         return 1;
-      std::fprintf(stderr, "  (%u dofs, %d CG iterations)\n", N, its);
+      std::fprintf(stderr, "  (%u dofs, %d CG iterations%s)\n", N, its, v_cycle ? ", V-cycle over the degrees 1 .. p" : "");
 
       // ---- output_results(): interpolate_to_fine_grid = u_h at the vertices of every sub-cell (include/poly_utils.h:1196-1233)
       {

@@ -462,6 +462,38 @@ int pdh_restrict_and_add_device  (pdh_transfer *t, const double *d_fine,   doubl
 int pdh_prolongate(pdh_transfer *t, const double *coarse, double *fine);
 int pdh_restrict  (pdh_transfer *t, const double *fine,   double *coarse);
 
+/* p-transfer: the SAME polytopes at two polynomial degrees q = coarse_degree < p = fine_degree (pdh_ptransfer.hip) - the hierarchy
+ * every mesh has, nested or not.  Both bases live in the unit coordinates of the polytope's bounding box, so no box enters and every
+ * polytope has the same injection block:
+ *   FE_DGQ       the Kronecker power (first axis fastest) of ONE (p+1) x (q+1) matrix B[i][j] = l^q_j(node^p_i): the degree-q Lagrange
+ *                basis on its Gauss-Lobatto nodes at the degree-p Gauss-Lobatto nodes; applied by rectangular sum factorisation.
+ *   FE_AggloDGP  the basis is the orthonormal Legendre product basis of the box frame, a coarse function IS a fine one: the injection
+ *                is the index map between the two multi-index lists (2-D 1 -> 2: [0, 1, 3]), exact to the bit.
+ * All pointers of the description are caller-owned host memory, read during the call only.                                          */
+typedef struct pdh_ptransfer_desc
+{
+  int32_t dim, fine_degree, coarse_degree, basis;      /* 2|3; 1 <= coarse < fine <= 7; PDH_BASIS_DGQ | PDH_BASIS_AGGLODGP */
+  int32_t n_polytopes;                                 /* the same polytopes on both levels                              */
+  int32_t n_fine_rows, n_coarse_rows;                  /* lengths of the level vectors                                   */
+  const int32_t *fine_dof_offset, *coarse_dof_offset;  /* [n_polytopes] as pdh_problem.dof_offset                        */
+} pdh_ptransfer_desc;
+/* Host-only.  The refusals, in this order: PDH_EINVAL for a NULL description, dim other than 2 or 3, an unknown basis;
+ * PDH_EUNSUPPORTED for degrees outside 1 <= coarse_degree < fine_degree <= 7 (in 2-D this is also the h-transfer's bound of 64 fine dofs
+ * per polytope); PDH_EINVAL for n_polytopes <= 0, NULL offsets, dof ranges [off, off + n) that overlap or leave [0, n_rows) on either
+ * level.  pdh_last_error(NULL) says which.                                                                                           */
+int pdh_check_ptransfer(const pdh_ptransfer_desc *d);
+/* Host-only, FE_DGQ (FE_AggloDGP: PDH_EINVAL): out [p+1][q+1], B[i][j] as above, from the 1-D basis behind the kernels' tables. */
+int pdh_ptransfer_matrix_1d(const pdh_ptransfer_desc *d, double *out);
+/* Host-only, FE_AggloDGP (FE_DGQ: PDH_EINVAL): out [n coarse dofs per polytope], the fine dof that IS coarse dof j. */
+int pdh_ptransfer_index_map(const pdh_ptransfer_desc *d, int32_t *out);
+/* The same opaque pdh_transfer as pdh_transfer_create gives, on the device and stream of `ctx` (no resident problem needed): everything
+ * above that takes one - pdh_prolongate*, pdh_restrict*, pdh_transfer_destroy - and pdh_mg_create serve it.  Runs pdh_check_ptransfer;
+ * uploads the two offset lists (and the index map); the 1-D matrix travels with every launch.  Every sum has a fixed order, no atomics:
+ * the same call on the same data gives the same bits; FE_AggloDGP transfers copy values and are exact.  Rows that belong to no polytope
+ * are not touched by the _device entries; prolongate_and_add leaves the fine FE_AggloDGP dofs outside the image untouched.
+ * pdh_galerkin_device on such a transfer is PDH_EUNSUPPORTED: coarse degrees are re-assembled on their own description.              */
+int pdh_ptransfer_create(pdh_ctx *ctx, const pdh_ptransfer_desc *d, pdh_transfer **out);
+
 /* Coarse level matrix as the Galerkin product A_c = P^T A_f P (pdh_galerkin.hip): the reference's AmgProjector::compute_level_matrices
  * (include/multigrid_amg.h:267-305) over the injection of the transfer, without the injection matrix.  With par() the parent map and B_X
  * the Kronecker injection block of fine polytope X,

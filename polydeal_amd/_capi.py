@@ -87,6 +87,12 @@ class pdh_transfer_desc(C.Structure):
                 ("coarse_dof_offset", C.c_void_p), ("parent", C.c_void_p)]
 
 
+class pdh_ptransfer_desc(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("fine_degree", C.c_int32), ("coarse_degree", C.c_int32), ("basis", C.c_int32),
+                ("n_polytopes", C.c_int32), ("n_fine_rows", C.c_int32), ("n_coarse_rows", C.c_int32),
+                ("fine_dof_offset", C.c_void_p), ("coarse_dof_offset", C.c_void_p)]
+
+
 class pdh_galerkin_level(C.Structure):
     _fields_ = [("n_slots", C.c_int32), ("n_rows_owned", C.c_int32), ("n_rows", C.c_int32), ("exchange_mode", C.c_int32),
                 ("device", C.c_int32), ("blk_ptr", C.c_void_p), ("blk_dof", C.c_void_p), ("dof_offset", C.c_void_p)]
@@ -122,13 +128,14 @@ EXPORTS = [
     "pdh_residual_device", "pdh_check_transfer", "pdh_transfer_children", "pdh_transfer_create",
     "pdh_transfer_destroy", "pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device",
     "pdh_restrict_and_add_device", "pdh_prolongate", "pdh_restrict",
+    "pdh_check_ptransfer", "pdh_ptransfer_index_map", "pdh_ptransfer_create",
     "pdh_setup_direct", "pdh_mg_create", "pdh_mg_destroy", "pdh_mg_vcycle_device",
     "pdh_set_smoother_precision", "pdh_smoother_precision", "pdh_smoother_vmult_device",
     "pdh_galerkin_plan", "pdh_galerkin_device",
     "pdh_setup_matrix_free", "pdh_matrix_free_vmult", "pdh_matrix_free_vmult_device", "pdh_set_smoother_operator", "pdh_smoother_operator",
 ]
 
-# (pdh_transfer_matrices_1d is bound below like the others; tests/test_capi_cpu.py matches this list against the names of
+# (pdh_transfer_matrices_1d and pdh_ptransfer_matrix_1d are bound below like the others; tests/test_capi_cpu.py matches this list against the names of
 # include/polydeal_hip.h that consist of letters and underscores)
 _lib = None
 
@@ -217,6 +224,10 @@ def _bind(lib):
     for name in ("pdh_prolongate_device", "pdh_prolongate_and_add_device", "pdh_restrict_device", "pdh_restrict_and_add_device",
                  "pdh_prolongate", "pdh_restrict"):
         getattr(lib, name).argtypes = [pdh_transfer_p, C.c_void_p, C.c_void_p]
+    lib.pdh_check_ptransfer.argtypes = [P(pdh_ptransfer_desc)]
+    lib.pdh_ptransfer_matrix_1d.argtypes = [P(pdh_ptransfer_desc), C.c_void_p]
+    lib.pdh_ptransfer_index_map.argtypes = [P(pdh_ptransfer_desc), C.c_void_p]
+    lib.pdh_ptransfer_create.argtypes = [pdh_ctx_p, P(pdh_ptransfer_desc), P(C.c_void_p)]
     lib.pdh_setup_direct.argtypes = [pdh_ctx_p, P(pdh_direct_info)]
     lib.pdh_mg_create.argtypes = [C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
     lib.pdh_mg_destroy.argtypes = [pdh_mg_p]
@@ -371,6 +382,48 @@ class TransferDesc:
         return ptr, idx
 
 
+class PTransferDesc:
+    """Owns the NumPy arrays behind a pdh_ptransfer_desc: the SAME polytopes at a lower (coarse) and a higher (fine) degree of one kind
+    of basis; first dof of every polytope on both levels."""
+
+    def __init__(self, *, dim, fine_degree, coarse_degree, fine_dof_offset, coarse_dof_offset, n_fine_rows=None, n_coarse_rows=None,
+                 basis=PDH_BASIS_DGQ):
+        import math
+
+        self.fine_dof_offset = np.ascontiguousarray(fine_dof_offset, dtype=np.int32)
+        self.coarse_dof_offset = np.ascontiguousarray(coarse_dof_offset, dtype=np.int32)
+        self.dim, self.fine_degree, self.coarse_degree, self.basis = int(dim), int(fine_degree), int(coarse_degree), int(basis)
+        self.n_polytopes = len(self.fine_dof_offset)
+        if self.fine_dof_offset.ndim != 1 or self.coarse_dof_offset.shape != (self.n_polytopes,):
+            raise ValueError("fine_dof_offset and coarse_dof_offset [n_polytopes]")
+
+        def n(degree):
+            return (degree + 1) ** self.dim if self.basis == PDH_BASIS_DGQ else math.comb(max(degree, 0) + self.dim, self.dim)
+        self.n_f, self.n_c = n(self.fine_degree), n(self.coarse_degree)
+        self.n_fine_rows = self.n_polytopes * self.n_f if n_fine_rows is None else int(n_fine_rows)
+        self.n_coarse_rows = self.n_polytopes * self.n_c if n_coarse_rows is None else int(n_coarse_rows)
+        self.c = pdh_ptransfer_desc(self.dim, self.fine_degree, self.coarse_degree, self.basis, self.n_polytopes, self.n_fine_rows,
+                                    self.n_coarse_rows, self.fine_dof_offset.ctypes.data, self.coarse_dof_offset.ctypes.data)
+
+    _chk = staticmethod(TransferDesc._chk)
+
+    def check(self):
+        """pdh_check_ptransfer: host only, no GPU."""
+        self._chk(load_library().pdh_check_ptransfer(C.byref(self.c)))
+
+    def matrix_1d(self):
+        """FE_DGQ, [p+1][q+1]: B[i][j] = l^q_j(node^p_i), the 1-D factor of every injection block (host only)."""
+        out = np.empty((self.fine_degree + 1, self.coarse_degree + 1))
+        self._chk(load_library().pdh_ptransfer_matrix_1d(C.byref(self.c), out.ctypes.data))
+        return out
+
+    def index_map(self):
+        """FE_AggloDGP, [n_c]: the fine dof that is coarse dof j (host only)."""
+        out = np.empty(self.n_c, dtype=np.int32)
+        self._chk(load_library().pdh_ptransfer_index_map(C.byref(self.c), out.ctypes.data))
+        return out
+
+
 class GalerkinLevel:
     """Owns the NumPy arrays behind a pdh_galerkin_level: the block lists of one level's resident rows (slot s = polytope s; blk_dof
     [blk_ptr[s] + t] = first global dof of the t-th block of its rows in value order) and what the refusals of galerkin_plan read."""
@@ -399,13 +452,14 @@ def galerkin_plan(desc: TransferDesc, fine: GalerkinLevel, coarse: GalerkinLevel
 
 
 class Transfer:
-    """pdh_transfer wrapper: prolongation / restriction between two nested levels on the device and stream of `ctx`, which needs no
-    resident problem.  Close it before its context."""
+    """pdh_transfer wrapper: prolongation / restriction between two nested levels (a TransferDesc) or two degrees on the same polytopes
+    (a PTransferDesc) on the device and stream of `ctx`, which needs no resident problem.  Close it before its context."""
 
-    def __init__(self, ctx, desc: TransferDesc):
+    def __init__(self, ctx, desc):
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
         h = C.c_void_p()
-        ctx._chk(self.lib.pdh_transfer_create(ctx.h, C.byref(desc.c), C.byref(h)))
+        create = self.lib.pdh_ptransfer_create if isinstance(desc, PTransferDesc) else self.lib.pdh_transfer_create
+        ctx._chk(create(ctx.h, C.byref(desc.c), C.byref(h)))
         self.h = h
 
     def _dev(self, fn, d_src, d_dst):

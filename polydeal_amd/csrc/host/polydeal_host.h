@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <fstream>
 #include <map>
@@ -1822,6 +1823,50 @@ struct TransferDescription
   }
   TransferDescription(const TransferDescription &) = delete;
   TransferDescription &operator=(const TransferDescription &) = delete;
+};
+
+// The pdh_ptransfer_desc of two handlers that hold the SAME polytopes - the same count and bit-equal boxes in the same order - with the
+// same kind of basis at a lower (coarse) and a higher (fine) degree: owns the arrays `c` points to.
+struct PTransferDescription
+{
+  std::vector<int32_t> fine_dof_offset, coarse_dof_offset;
+  pdh_ptransfer_desc c{};
+  PTransferDescription(const AgglomerationHandler &coarse_ah, const AgglomerationHandler &fine_ah)
+  {
+    const FiniteElement &fc = coarse_ah.get_fe(), &ff = fine_ah.get_fe();
+    if (fc.dim != ff.dim || fc.basis != ff.basis)
+      throw std::invalid_argument("p-transfer: the two handlers hold different kinds of basis (FE_DGQ and FE_AggloDGP, or 2-D and 3-D)");
+    if (fc.degree >= ff.degree)
+      throw std::invalid_argument("p-transfer: the coarse degree " + std::to_string(fc.degree) + " is not below the fine degree " +
+                                  std::to_string(ff.degree));
+    const int nA = (int)coarse_ah.n_agglomerates();
+    if (nA != (int)fine_ah.n_agglomerates())
+      throw std::invalid_argument("p-transfer: different polytopes: " + std::to_string(nA) + " on the coarse level, " +
+                                  std::to_string(fine_ah.n_agglomerates()) + " on the fine one");
+    for (int P = 0; P < nA; ++P)
+      for (int c = 0; c < fc.dim; ++c) // (bit-equal: compared as bytes, lower then upper corner)
+        if (std::memcmp(&coarse_ah.bbox(P)[c], &fine_ah.bbox(P)[c], sizeof(double)) != 0 ||
+            std::memcmp(&coarse_ah.bbox(P)[3 + c], &fine_ah.bbox(P)[3 + c], sizeof(double)) != 0)
+          throw std::invalid_argument("p-transfer: different polytopes: the boxes of polytope " + std::to_string(P) + " differ");
+    fine_dof_offset.resize((size_t)nA);
+    coarse_dof_offset.resize((size_t)nA);
+    for (int P = 0; P < nA; ++P)
+      {
+        fine_dof_offset[(size_t)P] = fine_ah.dof_offset_of(P);
+        coarse_dof_offset[(size_t)P] = coarse_ah.dof_offset_of(P);
+      }
+    c.dim = fc.dim;
+    c.fine_degree = ff.degree;
+    c.coarse_degree = fc.degree;
+    c.basis = fc.basis;
+    c.n_polytopes = nA;
+    c.n_fine_rows = (int32_t)fine_ah.n_dofs();
+    c.n_coarse_rows = (int32_t)coarse_ah.n_dofs();
+    c.fine_dof_offset = fine_dof_offset.data();
+    c.coarse_dof_offset = coarse_dof_offset.data();
+  }
+  PTransferDescription(const PTransferDescription &) = delete;
+  PTransferDescription &operator=(const PTransferDescription &) = delete;
 };
 
 // MGTransferAgglomeration (reference include/multigrid_amg.h:439-490) between two nested handlers, applied on the device of `ctx`

@@ -1,18 +1,23 @@
 // pdh_capi_transfer.cpp — device driver of the C ABI, level transfers (kernels: pdh_transfer.hip; planner: pdh_transfer_plan.cpp).  A
 // transfer owns its tables on the device of the context it was created on and launches on that context's stream; it needs no resident
 // problem there.  The Galerkin product of the two levels a transfer connects (kernel: pdh_galerkin.hip; planner: pdh_galerkin_plan.cpp)
-// is the one entry that does: it reads the resident rows of the transfer's context and writes those of the coarse one.
+// is the one entry that does: it reads the resident rows of the transfer's context and writes those of the coarse one.  A p-transfer
+// (pdh_ptransfer_create; kernels: pdh_ptransfer.hip) is the same pdh_transfer of another kind: every entry dispatches on it.
 #include "pdh_ctx.h"
 #include "pdh_galerkin.h"
 #include "pdh_launch.h"
+#include "pdh_ptransfer.h"
 #include "pdh_transfer.h"
 
 struct pdh_transfer
 {
+  enum Kind { H_NESTED, P_DGQ, P_AGGLODGP };
   pdh_ctx *ctx = nullptr;
+  Kind kind = H_NESTED;
   int dim = 0, n1d = 0;
   int64_t n_fine_rows = 0, n_coarse_rows = 0;
-  PdhTransferArgs args{};
+  PdhTransferArgs args{};   // H_NESTED
+  PdhPTransferArgs pargs{}; // P_*
   std::vector<void *> allocs;                              // every hipMalloc of the set-up; args points into these
   DevBuf in{DevBuf::slack}, out{DevBuf::slack};            // staging copies of pdh_prolongate / pdh_restrict
   // pdh_galerkin_device: host copies of what its planner reads of the description, and the plan on the device - valid for the coarse
@@ -85,6 +90,46 @@ extern "C" int pdh_transfer_create(pdh_ctx *ctx, const pdh_transfer_desc *d, pdh
   return PDH_OK;
 }
 
+extern "C" int pdh_ptransfer_create(pdh_ctx *ctx, const pdh_ptransfer_desc *d, pdh_transfer **out)
+{
+  PDH_TRY(need_ctx(ctx));
+  if (!out)
+    return fail(ctx, PDH_EINVAL, "out is required");
+  *out = nullptr;
+  PdhPTransferPlan plan;
+  PDH_TRY(pdh_plan_ptransfer(ctx->err, d, plan));
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  pdh_transfer *t = new pdh_transfer;
+  t->ctx = ctx;
+  t->kind = d->basis == PDH_BASIS_DGQ ? pdh_transfer::P_DGQ : pdh_transfer::P_AGGLODGP;
+  t->dim = d->dim;
+  t->n1d = d->fine_degree + 1;
+  t->degree = d->fine_degree;
+  t->n_fine_rows = d->n_fine_rows;
+  t->n_coarse_rows = d->n_coarse_rows;
+  PdhPTransferArgs &A = t->pargs;
+  A.n_polytopes = d->n_polytopes;
+  A.nf1d = d->fine_degree + 1;
+  A.nc1d = d->coarse_degree + 1;
+  A.n_f = plan.n_f;
+  A.n_c = plan.n_c;
+  std::copy(plan.B.begin(), plan.B.end(), A.B);
+  int rc = upload_in(ctx, t->allocs, d->fine_dof_offset, (size_t)d->n_polytopes, &A.fine_off, "fine_dof_offset");
+  if (rc == PDH_OK)
+    rc = upload_in(ctx, t->allocs, d->coarse_dof_offset, (size_t)d->n_polytopes, &A.coarse_off, "coarse_dof_offset");
+  if (rc == PDH_OK && t->kind == pdh_transfer::P_AGGLODGP)
+    rc = upload_in(ctx, t->allocs, plan.map.data(), plan.map.size(), &A.map, "index map");
+  if (rc == PDH_OK && t->kind == pdh_transfer::P_AGGLODGP)
+    rc = upload_in(ctx, t->allocs, plan.inv.data(), plan.inv.size(), &A.inv, "inverse index map");
+  if (rc != PDH_OK)
+    {
+      delete t;
+      return rc;
+    }
+  *out = t;
+  return PDH_OK;
+}
+
 extern "C" void pdh_transfer_destroy(pdh_transfer *t)
 {
   if (!t)
@@ -103,6 +148,8 @@ void pdh_transfer_info(const pdh_transfer *t, pdh_ctx **ctx, int64_t *n_fine_row
 
 hipError_t pdh_transfer_launch(const pdh_transfer *t, bool restriction, int add, const double *src, double *dst, hipStream_t stream)
 {
+  if (t->kind != pdh_transfer::H_NESTED)
+    return pdh_launch_ptransfer(t->dim, t->kind == pdh_transfer::P_DGQ, restriction, add, &t->pargs, src, dst, stream);
   return restriction ? pdh_launch_restrict(t->dim, t->n1d, add, &t->args, src, dst, stream)
                      : pdh_launch_prolongate(t->dim, t->n1d, add, &t->args, src, dst, stream);
 }
@@ -128,7 +175,7 @@ static int prolongate_device(pdh_transfer *t, const double *d_coarse, double *d_
 {
   PDH_TRY(transfer_checks(t, d_coarse, d_fine));
   PDH_HIP(t->ctx, hipSetDevice(t->ctx->device));
-  PDH_HIP(t->ctx, pdh_launch_prolongate(t->dim, t->n1d, add, &t->args, d_coarse, d_fine, t->ctx->stream));
+  PDH_HIP(t->ctx, pdh_transfer_launch(t, false, add, d_coarse, d_fine, t->ctx->stream));
   return PDH_OK;
 }
 
@@ -136,7 +183,7 @@ static int restrict_device(pdh_transfer *t, const double *d_fine, double *d_coar
 {
   PDH_TRY(transfer_checks(t, d_coarse, d_fine));
   PDH_HIP(t->ctx, hipSetDevice(t->ctx->device));
-  PDH_HIP(t->ctx, pdh_launch_restrict(t->dim, t->n1d, add, &t->args, d_fine, d_coarse, t->ctx->stream));
+  PDH_HIP(t->ctx, pdh_transfer_launch(t, true, add, d_fine, d_coarse, t->ctx->stream));
   return PDH_OK;
 }
 
@@ -251,6 +298,9 @@ extern "C" int pdh_galerkin_device(pdh_transfer *t, pdh_ctx *coarse)
     return fail(fine, PDH_EINVAL, "pdh_galerkin_device: the coarse context is NULL");
   if (coarse == fine)
     return fail(fine, PDH_EINVAL, "pdh_galerkin_device: the coarse context is the transfer's own");
+  if (t->kind != pdh_transfer::H_NESTED)
+    return fail(fine, PDH_EUNSUPPORTED, "pdh_galerkin_device: a p-transfer has no Galerkin product here; coarse degrees are re-assembled on their own "
+                                        "description");
   if (!fine->prob.resident)
     return fail(fine, PDH_ESTATE, "pdh_galerkin_device called before pdh_set_problem on the fine context");
   if (!fine->prob.has_values)

@@ -484,6 +484,22 @@ void *pdhh_transfer_desc_create(void *coarse, void *fine)
 }
 const pdh_transfer_desc *pdhh_transfer_desc_c(void *th) { return &static_cast<Utils::TransferDescription *>(th)->c; }
 void pdhh_transfer_desc_destroy(void *th) { delete static_cast<Utils::TransferDescription *>(th); }
+// The pdh_ptransfer_desc of two handlers on the same polytopes (a lower and a higher degree of one kind of basis), independently owned;
+// free it with pdhh_ptransfer_desc_destroy.
+void *pdhh_ptransfer_desc_create(void *coarse, void *fine)
+{
+  try
+    {
+      return new Utils::PTransferDescription(static_cast<HandlerH *>(coarse)->ah, static_cast<HandlerH *>(fine)->ah);
+    }
+  catch (const std::exception &e)
+    {
+      g_host_err = e.what();
+      return nullptr;
+    }
+}
+const pdh_ptransfer_desc *pdhh_ptransfer_desc_c(void *th) { return &static_cast<Utils::PTransferDescription *>(th)->c; }
+void pdhh_ptransfer_desc_destroy(void *th) { delete static_cast<Utils::PTransferDescription *>(th); }
 // Utils::MGTransferAgglomeration through C on host vectors: which = 0 prolongate (dst [n_fine_dofs] overwritten), 1 prolongate_and_add,
 // 2 restrict_and_add (dst [n_coarse_dofs]).  One context and one transfer per call: the device path of the mirror end to end.
 int pdhh_mg_transfer_apply(void *coarse, void *fine, int device, int which, const double *src, int64_t n_src, double *dst, int64_t n_dst)

@@ -15,7 +15,8 @@
 #include "pdh_solve.h"
 #include "pdh_terms_tables.h"
 
-struct PdhTransferArgs; // pdh_transfer.h
+struct PdhTransferArgs;  // pdh_transfer.h
+struct PdhPTransferArgs; // pdh_ptransfer.h
 struct PdhGalerkinArgs; // pdh_galerkin.h
 
 // One resolved launch (host only).  kernel: host stub of the instantiation, NULL where nothing could be resolved (no such instantiation,
@@ -175,6 +176,11 @@ hipError_t pdh_launch_prolongate(int dim, int n1d, int add, const PdhTransferArg
 hipError_t pdh_launch_restrict(int dim, int n1d, int add, const PdhTransferArgs *A, const double *fine, double *coarse, hipStream_t stream);
 // r = b - r over n_rows entries (r holds A x)
 hipError_t pdh_launch_residual_sub(int64_t n_rows, const double *b, double *r, hipStream_t stream);
+
+// pdh_ptransfer.hip (dim 2 | 3; dgq: FE_DGQ by sum factorisation with A->nf1d 3 .. 8 > A->nc1d >= 2, else FE_AggloDGP by A->map / A->inv;
+// restriction: dst = coarse (+)= P^T src, else dst = fine (+)= P src; add: accumulate): one wave per max(1, 64 / n_f) polytopes
+hipError_t pdh_launch_ptransfer(int dim, int dgq, int restriction, int add, const PdhPTransferArgs *A, const double *src, double *dst,
+                                hipStream_t stream);
 
 // pdh_galerkin.hip (dim 2, n1d 2 .. 8 | dim 3, n1d 2 .. 4: at most 64 dofs per polytope)
 // coarse values = P^T (fine values) P: one wave per coarse block, its fine blocks in plan order

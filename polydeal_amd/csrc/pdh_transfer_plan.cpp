@@ -1,7 +1,9 @@
 // pdh_transfer_plan.cpp — the host-only planner of a level transfer (pdh_transfer.h): the refusals of pdh_check_transfer, the 1-D
-// matrices of every fine polytope and the children CSR that fixes the summation order of the restriction.  Plain C++ like pdh_plan.cpp:
-// no HIP header, no HIP call; the 1-D basis is the one behind the kernels' tables (pdh_basis.h).
+// matrices of every fine polytope and the children CSR that fixes the summation order of the restriction; and of a p-transfer
+// (pdh_ptransfer.h): the refusals of pdh_check_ptransfer, the one 1-D matrix of FE_DGQ and the index map of FE_AggloDGP.  Plain C++ like
+// pdh_plan.cpp: no HIP header, no HIP call; the 1-D basis and the multi-index lists are those behind the kernels' tables (pdh_basis.h).
 #include "pdh_transfer.h"
+#include "pdh_ptransfer.h"
 
 #include "pdh_basis.h"
 #include "pdh_plan_internal.h"
@@ -134,7 +136,102 @@ void children_csr(const pdh_transfer_desc *d, std::vector<int32_t> &ptr, std::ve
   for (int F = 0; F < d->n_fine; ++F) // ascending F: ascending inside every parent
     idx[(size_t)at[(size_t)d->parent[F]]++] = F;
 }
+
+// ---- p-transfers ----
+int p_basis(const pdh_ptransfer_desc *d) { return d->basis == PDH_BASIS_DGQ ? 0 : 1; }
+
+// every refusal of pdh_check_ptransfer, in the order of include/polydeal_hip.h
+int validate_p(std::string &err, const pdh_ptransfer_desc *d)
+{
+  if (!d)
+    return fail(err, PDH_EINVAL, "the p-transfer description is NULL");
+  if (d->dim != 2 && d->dim != 3)
+    return fail(err, PDH_EINVAL, "dim must be 2 or 3");
+  if (d->basis != PDH_BASIS_DGQ && d->basis != PDH_BASIS_AGGLODGP)
+    return fail(err, PDH_EINVAL, "unknown basis");
+  // (in 2-D this is also the bound of 64 fine dofs per polytope: (p + 1)^2 <= 64)
+  if (d->coarse_degree < 1 || d->fine_degree > 7 || d->coarse_degree >= d->fine_degree)
+    return fail(err, PDH_EUNSUPPORTED, "the degrees of a p-transfer must be 1 <= coarse_degree < fine_degree <= 7");
+  if (d->n_polytopes <= 0)
+    return fail(err, PDH_EINVAL, "n_polytopes must be positive");
+  if (!d->fine_dof_offset || !d->coarse_dof_offset)
+    return fail(err, PDH_EINVAL, "dof_offset (both levels) is required");
+  PDH_TRY(check_dof_ranges(err, "fine", d->fine_dof_offset, d->n_polytopes, pdh::n_dofs_per_cell(d->dim, d->fine_degree, p_basis(d)), d->n_fine_rows));
+  return check_dof_ranges(err, "coarse", d->coarse_dof_offset, d->n_polytopes, pdh::n_dofs_per_cell(d->dim, d->coarse_degree, p_basis(d)),
+                          d->n_coarse_rows);
+}
+
+// B[i][j] = l^q_j(node^p_i): Horner in the centred variable, in long double, rounded once - exactly as matrices_1d does
+void p_matrix_1d(int p, int q, double *out)
+{
+  const pdh::Basis1D basis = pdh::lagrange_basis(q);
+  const std::vector<long double> nodes = pdh::gauss_lobatto_nodes(p);
+  for (int i = 0; i <= p; ++i)
+    {
+      const long double t = nodes[(size_t)i] - 0.5L;
+      for (int j = 0; j <= q; ++j)
+        {
+          long double v = basis.coef[(size_t)j][(size_t)q];
+          for (int m = q - 1; m >= 0; --m)
+            v = v * t + basis.coef[(size_t)j][(size_t)m];
+          out[i * (q + 1) + j] = (double)v;
+        }
+    }
+}
+
+// map[j] = the fine dof with the multi-index of coarse dof j (FE_AggloDGP: every coarse multi-index is a fine one)
+std::vector<int32_t> p_index_map(int dim, int p, int q)
+{
+  const std::vector<uint32_t> fine = pdh::multi_indices(dim, p, 1), coarse = pdh::multi_indices(dim, q, 1);
+  std::vector<int32_t> map(coarse.size(), -1);
+  for (size_t j = 0; j < coarse.size(); ++j)
+    map[j] = (int32_t)(std::find(fine.begin(), fine.end(), coarse[j]) - fine.begin());
+  return map;
+}
 } // namespace
+
+int pdh_plan_ptransfer(std::string &err, const pdh_ptransfer_desc *d, PdhPTransferPlan &plan)
+{
+  PDH_TRY(validate_p(err, d));
+  plan.n_f = pdh::n_dofs_per_cell(d->dim, d->fine_degree, p_basis(d));
+  plan.n_c = pdh::n_dofs_per_cell(d->dim, d->coarse_degree, p_basis(d));
+  if (d->basis == PDH_BASIS_DGQ)
+    {
+      plan.B.resize((size_t)(d->fine_degree + 1) * (d->coarse_degree + 1));
+      p_matrix_1d(d->fine_degree, d->coarse_degree, plan.B.data());
+      return PDH_OK;
+    }
+  plan.map = p_index_map(d->dim, d->fine_degree, d->coarse_degree);
+  plan.inv.assign((size_t)plan.n_f, -1);
+  for (size_t j = 0; j < plan.map.size(); ++j)
+    plan.inv[(size_t)plan.map[j]] = (int32_t)j;
+  return PDH_OK;
+}
+
+extern "C" int pdh_check_ptransfer(const pdh_ptransfer_desc *d) { return validate_p(pdh_noctx_error(), d); }
+
+extern "C" int pdh_ptransfer_matrix_1d(const pdh_ptransfer_desc *d, double *out)
+{
+  PDH_TRY(validate_p(pdh_noctx_error(), d));
+  if (d->basis != PDH_BASIS_DGQ)
+    return fail(pdh_noctx_error(), PDH_EINVAL, "pdh_ptransfer_matrix_1d: FE_AggloDGP has an index map (pdh_ptransfer_index_map), no 1-D matrix");
+  if (!out)
+    return fail(pdh_noctx_error(), PDH_EINVAL, "pdh_ptransfer_matrix_1d: out is required");
+  p_matrix_1d(d->fine_degree, d->coarse_degree, out);
+  return PDH_OK;
+}
+
+extern "C" int pdh_ptransfer_index_map(const pdh_ptransfer_desc *d, int32_t *out)
+{
+  PDH_TRY(validate_p(pdh_noctx_error(), d));
+  if (d->basis != PDH_BASIS_AGGLODGP)
+    return fail(pdh_noctx_error(), PDH_EINVAL, "pdh_ptransfer_index_map: FE_DGQ has a 1-D matrix (pdh_ptransfer_matrix_1d), no index map");
+  if (!out)
+    return fail(pdh_noctx_error(), PDH_EINVAL, "pdh_ptransfer_index_map: out is required");
+  const std::vector<int32_t> map = p_index_map(d->dim, d->fine_degree, d->coarse_degree);
+  std::copy(map.begin(), map.end(), out);
+  return PDH_OK;
+}
 
 int pdh_plan_transfer(std::string &err, const pdh_transfer_desc *d, PdhTransferPlan &plan)
 {

@@ -88,6 +88,12 @@ def _lib():
         lib.pdhh_transfer_desc_c.restype = C.POINTER(_capi.pdh_transfer_desc)
         lib.pdhh_transfer_desc_destroy.argtypes = [C.c_void_p]
         lib.pdhh_transfer_desc_destroy.restype = None
+        lib.pdhh_ptransfer_desc_create.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pdhh_ptransfer_desc_create.restype = C.c_void_p
+        lib.pdhh_ptransfer_desc_c.argtypes = [C.c_void_p]
+        lib.pdhh_ptransfer_desc_c.restype = C.POINTER(_capi.pdh_ptransfer_desc)
+        lib.pdhh_ptransfer_desc_destroy.argtypes = [C.c_void_p]
+        lib.pdhh_ptransfer_desc_destroy.restype = None
         lib.pdhh_mg_transfer_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         _ready = True
     return lib
@@ -542,6 +548,25 @@ def transfer_description(coarse_ah: AgglomerationHandler, fine_ah: Agglomeration
                                   parent=arr(c.parent, C.c_int32, (c.n_fine,)), n_fine_rows=c.n_fine_rows, n_coarse_rows=c.n_coarse_rows)
     finally:
         lib.pdhh_transfer_desc_destroy(th)
+
+
+def p_transfer_description(coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler):
+    """_capi.PTransferDesc of two handlers that hold the same polytopes (the same count, bit-equal boxes in the same order) and the same
+    kind of basis, the coarse one at the lower degree (Utils::PTransferDescription); HostError otherwise."""
+    lib = _lib()
+    th = lib.pdhh_ptransfer_desc_create(coarse_ah.h, fine_ah.h)
+    if not th:
+        _raise()
+    try:
+        c = lib.pdhh_ptransfer_desc_c(th).contents
+
+        def arr(addr):
+            return np.array((C.c_int32 * c.n_polytopes).from_address(int(addr)))
+        return _capi.PTransferDesc(dim=c.dim, fine_degree=c.fine_degree, coarse_degree=c.coarse_degree, basis=c.basis,
+                                   fine_dof_offset=arr(c.fine_dof_offset), coarse_dof_offset=arr(c.coarse_dof_offset),
+                                   n_fine_rows=c.n_fine_rows, n_coarse_rows=c.n_coarse_rows)
+    finally:
+        lib.pdhh_ptransfer_desc_destroy(th)
 
 
 def mg_transfer_apply(coarse_ah: AgglomerationHandler, fine_ah: AgglomerationHandler, which, src, dst=None, device=0):

@@ -122,13 +122,31 @@ class MultigridHierarchy:
         self.contexts = []
 
 
-def _setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator="stored", sip_values=True):
-    """the solver of level 0, the smoother of every level above: what its set-up reported, and under 'smoother_operator' which operator
-    the level's smoother applies.  'matrix_free' is taken where the context grants the tables (PDH_EUNSUPPORTED: the level stays
-    'stored') and its values are the SIP assembly of its own description (sip_values)."""
+def _set_level_problem(ctx, ah, variant, diag_first):
+    """the description of one level handler becomes the resident problem of `ctx`: the Cartesian one where it is taken"""
+    from ._capi import PdhError
+    from .handler import HostError
+
+    flat = None
+    if ah.grid.dim == 3:
+        try:
+            flat = ah.flatten_cartesian(variant, diag_first, False)
+            ctx.set_problem(flat)
+        except (PdhError, HostError):
+            flat = None
+    if flat is None:
+        flat = ah.flatten(variant, diag_first, False)  # (no colind: nothing here reads the pattern back)
+        ctx.set_problem(flat)
+
+
+def _setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator="stored", sip_values=True, coarsest="direct"):
+    """the solver of level 0 (coarsest 'direct': the dense solve; 'chebyshev': one application of the smoother's polynomial), the smoother
+    of every level above: what its set-up reported, and under 'smoother_operator' which operator the level's smoother applies.
+    'matrix_free' is taken where the context grants the tables (PDH_EUNSUPPORTED: the level stays 'stored') and its values are the SIP
+    assembly of its own description (sip_values)."""
     from ._capi import PDH_EUNSUPPORTED, PdhError
 
-    info = dict(ctx.setup_direct() if l == 0 else ctx.setup_chebyshev(inner, degree=degree))
+    info = dict(ctx.setup_direct() if l == 0 and coarsest == "direct" else ctx.setup_chebyshev(inner, degree=degree))
     if l > 0 and smoother_precision == "f32":
         ctx.set_smoother_precision("f32")
     info["smoother_operator"] = "stored"
@@ -159,8 +177,7 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
     and whose values are the SIP assembly of its own polytopes - under 'galerkin' the finest only - takes the products of its smoother
     and its residual from them (Context.set_smoother_operator); the other levels stay 'stored'.  info[l]["smoother_operator"] says which
     is in force.  Returns a MultigridHierarchy; close() it."""
-    from ._capi import Context, Multigrid, PdhError
-    from .handler import HostError
+    from ._capi import Context, Multigrid
 
     variant = variant or SipVariant.assemble_dg_matrix()
     if inner is None:
@@ -179,16 +196,7 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
                 raise ValueError("FE passed to multigrid_hierarchy differs from a level handler's")
             ctx = Context(device)
             contexts.append(ctx)
-            flat = None
-            if ah.grid.dim == 3:
-                try:
-                    flat = ah.flatten_cartesian(variant, diag_first, False)
-                    ctx.set_problem(flat)
-                except (PdhError, HostError):
-                    flat = None
-            if flat is None:
-                flat = ah.flatten(variant, diag_first, False)  # (no colind: nothing here reads the pattern back)
-                ctx.set_problem(flat)
+            _set_level_problem(ctx, ah, variant, diag_first)
             if not galerkin:
                 ctx.assemble_device()
                 info.append(_setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator))
@@ -200,6 +208,70 @@ def multigrid_hierarchy(levels, fe: FiniteElement, variant: SipVariant | None = 
                 transfers[l - 1].galerkin_device(contexts[l - 1])
             info = [_setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator, l == len(contexts) - 1)
                     for l, ctx in enumerate(contexts)]
+        mg = Multigrid(contexts, transfers)
+    except Exception:
+        MultigridHierarchy(contexts, transfers, mg, info).close()
+        raise
+    return MultigridHierarchy(contexts, transfers, mg, info)
+
+
+def _level_pair_description(l, coarse_ah, fine_ah):
+    """the description of the transfer between two consecutive level handlers: a p-pair (the same polytopes, one kind of basis, a lower
+    degree below) or a nested h-pair of equal degree; anything else is a ValueError naming the pair"""
+    from .handler import HostError, p_transfer_description, transfer_description
+
+    who = "levels %d and %d" % (l - 1, l)
+    fc, ff = coarse_ah.fe, fine_ah.fe
+    if fc.dim != ff.dim or fc.basis != ff.basis:
+        raise ValueError(who + " hold different kinds of basis")
+    try:
+        if fc.degree == ff.degree:
+            return transfer_description(coarse_ah, fine_ah)
+        if fc.degree < ff.degree:
+            return p_transfer_description(coarse_ah, fine_ah)
+    except HostError as e:
+        raise ValueError("%s are neither a p-pair nor a nested h-pair: %s" % (who, e)) from e
+    raise ValueError("%s: the degree falls from %d to %d towards the finer level" % (who, fc.degree, ff.degree))
+
+
+def p_multigrid_hierarchy(handlers, variant=None, diag_first=True, degree=3, device=0, smoother_precision="f64",
+                          smoother_operator="stored", coarsest=None):
+    """A V-cycle over levels that differ in polynomial degree, in polytopes, or from pair to pair in either: `handlers` coarse to fine,
+    each with its own FE distributed; `variant`: one SipVariant for all levels, or a function of a level's FE where the scalars depend on
+    the degree (SipVariant.poisson_example).  Every consecutive pair is a p-pair - the same polytopes (count, bit-equal boxes, order) and kind
+    of basis, the lower degree below (handler.p_transfer_description) - or a nested h-pair of equal degree (handler.transfer_description);
+    anything else is a ValueError naming the pair.  A p-hierarchy needs no second mesh, so grown agglomerates, FE_AggloDGP and the
+    elements beyond 64 dofs have one.  Every level is assembled on its own description like multigrid_hierarchy does (coarse degrees are
+    re-assembled, there is no Galerkin product across degrees); its smoother is Chebyshev of `degree` over block Jacobi, over point
+    Jacobi where its element has more than 64 dofs.  `coarsest`: 'direct' (the dense solve, at most 1024 rows), 'chebyshev' (one
+    application of its smoother's polynomial), None: 'direct' up to 1024 rows.  smoother_precision and smoother_operator act per level
+    as in multigrid_hierarchy.  Returns a MultigridHierarchy; close() it."""
+    from ._capi import Context, Multigrid, Transfer
+
+    handlers = list(handlers)
+    if len(handlers) < 2:
+        raise ValueError("a hierarchy has at least two levels")
+    if smoother_precision not in ("f64", "f32"):
+        raise ValueError("smoother_precision must be 'f64' or 'f32'")
+    if smoother_operator not in ("stored", "matrix_free"):
+        raise ValueError("smoother_operator must be 'stored' or 'matrix_free'")
+    if coarsest not in (None, "direct", "chebyshev"):
+        raise ValueError("coarsest must be 'direct', 'chebyshev' or None")
+    if coarsest is None:
+        coarsest = "direct" if handlers[0].n_dofs <= 1024 else "chebyshev"
+    descriptions = [_level_pair_description(l, handlers[l - 1], handlers[l]) for l in range(1, len(handlers))]
+    contexts, transfers, info, mg = [], [], [], None
+    try:
+        for l, ah in enumerate(handlers):
+            ctx = Context(device)
+            contexts.append(ctx)
+            level_variant = variant(ah.fe) if callable(variant) else variant or SipVariant.assemble_dg_matrix()
+            _set_level_problem(ctx, ah, level_variant, diag_first)
+            ctx.assemble_device()
+            inner = "block_jacobi" if ah.fe.n_dofs_per_cell <= 64 else "jacobi"
+            info.append(_setup_level(ctx, l, inner, degree, smoother_precision, smoother_operator, coarsest=coarsest))
+            if l > 0:
+                transfers.append(Transfer(ctx, descriptions[l - 1]))
         mg = Multigrid(contexts, transfers)
     except Exception:
         MultigridHierarchy(contexts, transfers, mg, info).close()

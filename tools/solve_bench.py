@@ -49,6 +49,15 @@ the set-up; k_vmult, k_vmult_f32 and k_mf_vmult on the finest level, alternating
 1e-13, with the stored and the matrix-free smoother operator alternating twice each (and once each over F32 inverses with
 --smoother-f32); the stored and the matrix-free product on FE_AggloDGP(3) and on grown agglomerates of the same cells.  Conditions (fields
 mf_faster_than_stored_beyond_spread, same_iterations_within_one, matrix_free_solve_not_slower); mf_faster_than_f32 is recorded either way.
+
+p-multigrid section (--p-vcycle, alone; pdh_ptransfer_create, levels.p_multigrid_hierarchy), written to profiles/r13_p_multigrid.json
+unless --out says otherwise, ONE process, HIP events, medians of --reps: (a) prolongate + restrict of the p-pairs FE_DGQ 2 -> 3 and
+FE_AggloDGP 2 -> 3 on the headline polytopes next to one k_cheb_update of their fine level (field transfer_pair_under_cheb_update, the
+condition of the transfer section; the h-pair of profiles/r08_transfer.json is recorded beside it); (b) the headline solve with the
+h-hierarchy of FE_DGQ(3) and with "FE_DGQ(1) on polytopes of 32^3 .. 2^3 cells, then FE_DGQ(2) and FE_DGQ(3) on the 2^3 polytopes":
+iterations, ms per cycle, seconds, bytes of the level matrices; (c) FE_DGQ(3) on grown agglomerates of about 2^3 cells, which have no
+nested hierarchy: block-Jacobi CG against the p-V-cycle over the degrees 1 -> 2 -> 3 with a Chebyshev coarsest level.  (b) and (c) are
+reports: no condition is checked.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -750,6 +759,122 @@ def matrix_free_case(pa, torch, cells, reps, with_f32):
     return out
 
 
+def p_vcycle_case(pa, torch, cells, reps):
+    """the p-multigrid figures (profiles/r13_p_multigrid.json), one process:
+    (a) the prolongate + restrict pair of FE_DGQ 2 -> 3 and of FE_AggloDGP 2 -> 3 on the headline polytopes (2^3 cells) next to one
+        k_cheb_update of the fine level, the condition the h-transfers are held to in profiles/r08_transfer.json;
+    (b) the headline solve with the h-hierarchy of FE_DGQ(3) against the hierarchy "FE_DGQ(1) on polytopes of 32^3 .. 2^3 cells, then
+        FE_DGQ(2) and FE_DGQ(3) on the 2^3 polytopes": iterations, ms per cycle, seconds per solve, bytes of the level matrices;
+    (c) grown agglomerates of about 2^3 cells with FE_DGQ(3) (bench.py's dgq3_grown: no nested hierarchy exists): block-Jacobi CG against
+        the p-V-cycle over the degrees 1 -> 2 -> 3 with a Chebyshev coarsest level."""
+    from polydeal_amd._capi import PTransferDesc, Transfer
+    from polydeal_amd.levels import block_hierarchy, multigrid_hierarchy, p_multigrid_hierarchy
+
+    t0 = time.time()
+    stream = torch.cuda.current_stream().cuda_stream
+    grid = pa.BackgroundGrid.hyper_cube_refined(3, 0.0, 1.0, cells.bit_length() - 1)
+    vec = lambda n: torch.rand(n, dtype=torch.float64, device="cuda")
+    variant = pa.SipVariant.poisson_example
+    out = {"cells_per_axis": cells, "pairs": []}
+
+    def one_level(fe, block=2, grown=False):
+        ah = pa.AgglomerationHandler(grid)
+        if grown:
+            ah.define_grown_agglomerates(block ** 3, seed=1)
+        else:
+            ah.define_block_agglomerates(block)
+        ah.initialize_fe_values(fe.degree + 1, fe.degree + 1)
+        ah.distribute_agglomerated_dofs(fe)
+        return ah
+
+    # (a)
+    for mk, name in ((pa.FE_DGQ, "FE_DGQ"), (pa.FE_AggloDGP, "FE_AggloDGP")):
+        fe_c, fe_f = mk(3, 2), mk(3, 3)
+        ah = one_level(fe_f)
+        ctx = pa.Context(0)
+        ctx.set_stream(stream)
+        ctx.set_problem(ah.flatten(variant(fe_f), False, False))
+        ctx.assemble_device()
+        nA, n_f, n_c = ah.n_agglomerates, fe_f.n_dofs_per_cell, fe_c.n_dofs_per_cell
+        desc = PTransferDesc(dim=3, fine_degree=3, coarse_degree=2, basis=fe_f.basis, fine_dof_offset=[P * n_f for P in range(nA)],
+                             coarse_dof_offset=[P * n_c for P in range(nA)])  # (the numbering of distribute_agglomerated_dofs)
+        tr = Transfer(ctx, desc)
+        Nf, Nc = desc.n_fine_rows, desc.n_coarse_rows
+        xc, rf, xf, bf, yc = vec(Nc), vec(Nf), vec(Nf), vec(Nf), vec(Nc)
+        ctx.synchronize()
+        pro = event_times_ms(torch, lambda: tr.prolongate_device(xc.data_ptr(), xf.data_ptr()), reps)
+        res = event_times_ms(torch, lambda: tr.restrict_device(rf.data_ptr(), yc.data_ptr()), reps)
+        ctx.setup_chebyshev("block_jacobi", degree=1)
+        upd = event_times_ms(torch, lambda: ctx.precondition_device(bf.data_ptr(), xf.data_ptr()), reps)  # one k_cheb_update
+        moved = 8.0 * (Nf + Nc) + 8.0 * nA
+        rec = {"pair": "%s 2 -> 3" % name, "polytopes": nA, "fine_dofs": Nf, "coarse_dofs": Nc, "fine_dofs_per_polytope": n_f,
+               "prolongate_ms_median": median(pro), "prolongate_ms_min": min(pro), "restrict_ms_median": median(res),
+               "restrict_ms_min": min(res), "transfer_bytes": moved, "prolongate_GBps": moved / (median(pro) * 1e-3) / 1e9,
+               "restrict_GBps": moved / (median(res) * 1e-3) / 1e9, "cheb_update_ms_median": median(upd),
+               "transfer_pair_ms": median(pro) + median(res), "h_pair_ms_at_FE_DGQ3_r08": 0.087,
+               "transfer_pair_under_cheb_update": bool(median(pro) + median(res) < median(upd))}
+        out["pairs"].append(rec)
+        print(json.dumps(rec), flush=True)
+        tr.close()
+        ctx.close()
+        del ah
+
+    def solve(hier, label, handlers):
+        for c in hier.contexts:
+            c.set_stream(stream)
+        fin, N = hier.finest, handlers[-1].n_dofs
+        values = [c.stats()["n_values"] for c in hier.contexts]
+        b, x = vec(N), vec(N)
+        cy = event_times_ms(torch, lambda: hier.vcycle_device(b.data_ptr(), x.data_ptr(), True), reps)
+        xs = torch.rand(N, dtype=torch.float64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+        rhs, sol = torch.empty(N, dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.float64, device="cuda")
+        fin.vmult_device(xs.data_ptr(), rhs.data_ptr())
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        si = hier.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+        wall = time.perf_counter() - w0
+        rec = {"hierarchy": label, "rows": [h.n_dofs for h in handlers], "polytopes": [h.n_agglomerates for h in handlers],
+               "coarsest": "direct" if "pivot_min" in hier.info[0] else "one Chebyshev(3) application", "iterations": si["iterations"],
+               "vcycle_ms_median": median(cy), "vcycle_ms_min": min(cy), "solve_wall_s": wall, "residual": si["residual"],
+               "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs)), "level_matrix_bytes": 8.0 * sum(values),
+               "coarser_levels_over_finest_bytes": sum(values[:-1]) / values[-1]}
+        print(json.dumps(rec), flush=True)
+        return rec, rhs, xs
+
+    # (b)
+    fe3 = pa.FE_DGQ(3, 3)
+    blocks = [b for b in (32, 16, 8, 4, 2) if 2 * b <= cells]
+    handlers = block_hierarchy(grid, fe3, blocks)
+    hier = multigrid_hierarchy(handlers, fe3, variant(fe3), diag_first=True, degree=3)
+    out["headline"] = [solve(hier, "h: FE_DGQ(3) on polytopes of %s cells per axis" % blocks, handlers)[0]]
+    hier.close()
+    fine3 = handlers[-1]
+    del handlers, hier
+    handlers = block_hierarchy(grid, pa.FE_DGQ(3, 1), blocks) + [one_level(pa.FE_DGQ(3, 2)), fine3]
+    hier = p_multigrid_hierarchy(handlers, variant, diag_first=True, degree=3)
+    out["headline"].append(solve(hier, "p-then-h: FE_DGQ(1) on polytopes of %s cells per axis, then FE_DGQ(2), FE_DGQ(3) on 2" % blocks, handlers)[0])
+    hier.close()
+    del handlers, hier, fine3
+    # (c)
+    handlers = [one_level(pa.FE_DGQ(3, q), grown=True) for q in (1, 2, 3)]
+    hier = p_multigrid_hierarchy(handlers, variant, diag_first=True, degree=3)
+    rec, rhs, xs = solve(hier, "p: FE_DGQ 1 -> 2 -> 3 on grown agglomerates of about 2^3 cells", handlers)
+    fin, N = hier.finest, handlers[-1].n_dofs
+    fin.setup_preconditioner("block_jacobi")  # detaches the mg
+    sol = torch.zeros(N, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    w0 = time.perf_counter()
+    si = fin.solve_cg_device(rhs.data_ptr(), sol.data_ptr(), rel_tol=1e-13)
+    wall = time.perf_counter() - w0
+    bj = {"preconditioner": "block Jacobi", "iterations": si["iterations"], "solve_wall_s": wall, "residual": si["residual"],
+          "rel_error_vs_x_star": float(torch.linalg.norm(sol - xs) / torch.linalg.norm(xs))}
+    print(json.dumps(bj), flush=True)
+    out["dgq3_grown"] = {"p_vcycle": rec, "block_jacobi": bj, "wall_over_block_jacobi": rec["solve_wall_s"] / wall}
+    hier.close()
+    out["case_wall_s"] = time.time() - t0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
@@ -765,11 +890,23 @@ def main():
                          "(default --out: profiles/r12_matrix_free.json)")
     ap.add_argument("--galerkin", action="store_true",
                     help="with --vcycle: the Galerkin-product section alone (default --out: profiles/r11_galerkin.json)")
+    ap.add_argument("--p-vcycle", action="store_true",
+                    help="the p-multigrid section alone: p-transfer pairs, the headline solve over a p-then-h hierarchy, dgq3_grown "
+                         "(default --out: profiles/r13_p_multigrid.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.p_vcycle:
+        out = {"tool": "tools/solve_bench.py --p-vcycle", "version": pa.load_library().pdh_version().decode(),
+               "device": torch.cuda.get_device_name(0)}
+        out.update(p_vcycle_case(pa, torch, args.cells, args.reps))
+        doc = json.dumps(out, indent=1)
+        with open(args.out or os.path.join(ROOT, "profiles", "r13_p_multigrid.json"), "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     if args.matrix_free:
         if not args.vcycle or args.galerkin:
             ap.error("--matrix-free goes with --vcycle (and --smoother-f32)")
