@@ -472,7 +472,8 @@ static void resolve_launches(pdh_ctx *ctx, const Packed &K, const PlanSwitches &
   else if (pr.row_kernel == RowKernel::terms)
     {
       const char *why = nullptr;
-      pr.row = pdh_resolve_terms(&D, &pr.terms, pr.n_owned, cus, sw.terms_wg_waves, sw.terms_wg_batch, &why);
+      pr.row = pdh_resolve_terms(&D, &pr.terms, pr.n_owned, cus, sw.terms_wg_waves, sw.terms_wg_batch, pdht::WG_STORE_AUX,
+                                 pdht::WG_DRAIN ? 1 : 0, &why);
       if (!pr.row.kernel)
         *why_row = why;
     }
@@ -831,6 +832,32 @@ extern "C" int pdh_debug_rows_stamps(pdh_ctx *ctx, long long *out)
   PDH_HIP(ctx, hipMemcpy(out, src, (size_t)ctx->prob.n_owned * 16 * sizeof(long long), hipMemcpyDeviceToHost));
   return PDH_OK;
 }
+
+#ifdef PDHT_VARIANTS
+// Diagnostic (builds with -DPDHT_VARIANTS only): from now on the resident FE_DGQ(3) problem is assembled by k_terms_wg with this store
+// policy of the writers - order 0 (piece-major: the one there is); aux 18 (sc1 nt), drain 1: the library's; aux 2 (nt), drain 0: the
+// baseline it was chosen against - resolved like the launch of set-up (the switches as they stand now).  The variants of one context
+// write the same allocation: tools/paired_bench.py.
+extern "C" int pdh_debug_terms_wg_variant(pdh_ctx *ctx, int order, int aux, int drain)
+{
+  if (!ctx || !ctx->prob.resident || ctx->prob.row_kernel != RowKernel::terms || ctx->prob.dev.n1d != 4 || ctx->prob.dev.n != 64)
+    return fail(ctx, PDH_ESTATE, "no FE_DGQ(3) term-kernel problem resident");
+  if (order != 0)
+    return fail(ctx, PDH_EINVAL, "order must be 0 (piece-major)");
+  PDH_HIP(ctx, hipSetDevice(ctx->device));
+  PDH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const PlanSwitches sw = read_plan_switches();
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+  const char *why = nullptr;
+  const PdhLaunch L = pdh_resolve_terms(&ctx->prob.dev, &ctx->prob.terms, ctx->prob.n_owned, cus, sw.terms_wg_waves, sw.terms_wg_batch, aux,
+                                        drain, &why);
+  if (!L.kernel)
+    return fail(ctx, PDH_EUNSUPPORTED, why);
+  ctx->prob.row = L;
+  return PDH_OK;
+}
+#endif
 
 extern "C" int pdh_set_overlap(pdh_ctx *ctx, int enabled)
 {

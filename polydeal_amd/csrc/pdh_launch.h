@@ -102,8 +102,11 @@ hipError_t pdh_launch_rows(const PdhLaunch *L, bool zero_sched, const PdhDev *P,
 
 // pdh_terms.hip; FE_DGQ(3) kernel: wg_waves: writer waves of a workgroup, 4 | 8; its grid is min(count, cus), or, wg_batch > 0,
 // ceil(count / wg_batch) workgroups (PlanSwitches).  Nothing is resolved (kernel NULL) where that kernel would not be alone on its CU:
-// *why (never NULL) names the reason, and set-up fails with it.  Launches of one problem share its work counter: one stream, in order
-PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int cus, int wg_waves, int wg_batch, const char **why);
+// *why (never NULL) names the reason, and set-up fails with it.  Launches of one problem share its work counter: one stream, in order.
+// store_aux, drain: how that kernel's writers store (pdh_terms_tables.h: WG_STORE_AUX, WG_DRAIN are what set-up asks for and all the
+// library instantiates; -DPDHT_VARIANTS builds resolve the other policies for pdh_debug_terms_wg_variant)
+PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int cus, int wg_waves, int wg_batch, int store_aux, int drain,
+                            const char **why);
 hipError_t pdh_launch_terms(const PdhLaunch *L, const PdhDev *P, const PdhTerms *T, int count, hipStream_t stream);
 hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T, double *out, int count, hipStream_t stream);
 

@@ -29,7 +29,11 @@ extern "C" hipError_t pdh_launch_terms_gather(const PdhDev *P, const PdhTerms *T
 // set-up.  The workgroups take the polytopes from a device-wide counter: min(count, cus) of them, or ceil(count / wg_batch) on request
 // (PDH_TERMS_WG_BATCH, so that a small test reaches workgroups of several polytopes).  Rules of up to 4 / up to 8 points per direction
 // (PdhTerms::task_pts) have their own instantiations.
-extern "C" PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int cus, int wg_waves, int wg_batch, const char **why)
+// store_aux, drain: how the writers of the FE_DGQ(3) kernel store (template arguments AUX, DRAIN of its body).  The library holds the
+// defaults of pdh_terms_tables.h alone (k_terms_wg); a -DPDHT_VARIANTS build also the baseline they were measured against
+// (k_terms_wg_base: WG_BASE_*).
+extern "C" PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int count, int cus, int wg_waves, int wg_batch, int store_aux,
+                                       int drain, const char **why)
 {
   PdhLaunch L{};
   *why = "no instantiation of the term kernel for this element, or a grid beyond 2^31 - 1 workgroups";
@@ -39,8 +43,21 @@ extern "C" PdhLaunch pdh_resolve_terms(const PdhDev *P, const PdhTerms *T, int c
     pdh_for_bools(
       [&](auto eight_, auto shifted_, auto small_) {
         constexpr int W = decltype(eight_)::value ? 8 : 4, PM = decltype(small_)::value ? 4 : 8;
+        constexpr bool SH = decltype(shifted_)::value;
         constexpr unsigned block = PDH_WAVE * (W + pdht::WG_BUILDERS);
-        const PdhTermsKernel k = pdht::k_terms_wg<W, decltype(shifted_)::value, PM>;
+        PdhTermsKernel k = nullptr;
+        if (store_aux == pdht::WG_STORE_AUX && (drain != 0) == pdht::WG_DRAIN)
+          k = pdht::k_terms_wg<W, SH, PM>;
+#ifdef PDHT_VARIANTS
+        else if (store_aux == pdht::WG_BASE_STORE_AUX && (drain != 0) == pdht::WG_BASE_DRAIN)
+          k = pdht::k_terms_wg_base<W, SH, PM>;
+#endif
+        if (!k)
+          {
+            *why = "FE_DGQ(3) term kernel: this store policy of the writers is not instantiated (the library: sc1 nt stores, drained; "
+                   "diagnostic builds -DPDHT_VARIANTS also nt stores left in flight)";
+            return;
+          }
         int dev = 0, cu_lds = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || cu_lds <= 0)

@@ -81,6 +81,15 @@ struct Kind
   PDH_HD static constexpr int sym(int k, int l) { return k <= l ? l * (l + 1) / 2 + k : k * (k + 1) / 2 + l; }
 };
 
+// pdh_terms_wg.h, how its writers store a polytope's rows: the cache-policy bits of the row stores (gfx940+: 1 = sc0, 2 = nt, 16 = sc1)
+// and whether a writer waits for its stores before the barrier that ends a step.  The one form the library ships: sc1|nt, drained -
+// 2.6-3.3 % ahead of nt stores left in flight on each of eight contexts, paired on the same allocation (profiles/r14_paired_variants.txt)
+constexpr int WG_STORE_AUX = 18;
+constexpr bool WG_DRAIN = true;
+// the form before, which -DPDHT_VARIANTS builds keep as the baseline of tools/paired_bench.py
+constexpr int WG_BASE_STORE_AUX = 2;
+constexpr bool WG_BASE_DRAIN = false;
+
 // LDS of a workgroup in doubles (host and device agree through this one function)
 PDH_HD constexpr int terms_rec_doubles(int maxruns) { return (TERMS_HDR + maxruns * TERMS_ENT + 1) & ~1; }
 // Two-phase tables (SPLIT): the D / M / K tables are needed by the diagonal block only, the X tables by the row pieces only.  Made

@@ -17,7 +17,13 @@
 //     (k + 1) & 1, whose data they requested a step earlier, and request the data of polytope k + 2.  ONE __syncthreads() ends the step:
 //     the writers last read buffer (k + 1) & 1 in step k - 1, before its barrier.  Every wave passes (polytopes of the workgroup) + 1
 //     barriers.  Loads and stores are separated BY WAVE: a writer makes no load from global memory (vmcnt retires in issue order - a load
-//     behind a burst of row stores waits for all of them), a builder no store.
+//     behind a burst of row stores waits for all of them), a builder no store;
+//   - the row stores are sc1|nt, and a writer waits for its own (vmcnt(0)) before the step's barrier: against nt stores left in flight
+//     over the barrier, timed in turn on the SAME resident problem (tools/paired_bench.py), -2.6 % to -3.3 % on each of eight contexts
+//     with the baseline 0.2 % apart from itself, and -1.5 % to -5 % from an eighth of the bench mesh to its grown agglomerates
+//     (profiles/r14_paired_variants.txt).  The ORDER of a wave's stores (its 8 rows of one piece, 3.5 KB apart, then the next piece) was
+//     set against whole rows in ascending address order in the store-only twin and is not what holds the stream back: row-major is 2-3 %
+//     slower than piece-major at their better policies (profiles/r14_probe_row_major.txt).
 // Builders (phase A: the lane tasks of pdh_terms.h, TermTasks): waves 0, 1 the (sub-face, tangential direction[, half]) tasks in
 // alternating chunks of 64, wave 2 the normal-direction tasks, wave 3 the (cell, direction[, half]) tasks - a lane's task, and with it
 // every address of a request, depends on the slot alone, so a request waits for nothing, not even the header (one round trip to HBM).
@@ -43,7 +49,7 @@
 #include "pdh_terms.h"
 
 // -DPDHT_STAMP (diagnostic builds): cycle counter -> stamps[slot][..]: the first writer wave at 0 .. 2, the last at 3 .. 5 (start of the
-// step, last store issued, barrier left); the first builder wave at 6 .. 8, the last at 9 .. 11 (loads of the NEXT polytope issued, tables
+// step, last store issued - and, where the writers drain, retired -, barrier left: 2 - 1 is the wait at the barrier alone); the first builder wave at 6 .. 8, the last at 9 .. 11 (loads of the NEXT polytope issued, tables
 // of this one done, barrier left)
 #ifdef PDHT_STAMP
 #define PDHW_MARK(s, base, k)                                                                                         \
@@ -60,13 +66,16 @@
 
 namespace pdht
 {
-// gfx940+ cache-policy bits of the row stores: 1 = sc0, 2 = nt, 16 = sc1
-constexpr int WG_STORE_AUX = 2;
 constexpr int WG_BUILDERS = 4; // builder waves of a workgroup
 constexpr int WG_TICKET = 2;   // the one that draws the tickets (normal-direction tasks: the least loads and arithmetic)
 
-template <int W, bool SHIFTED, int PMAX>
-__global__ void __launch_bounds__(PDH_WAVE *(W + WG_BUILDERS), 1) k_terms_wg(const PdhDev P, const PdhTerms T, const int n_owned)
+// The kernel's body.  AUX: cache-policy bits of the row stores (gfx940+: 1 = sc0, 2 = nt, 16 = sc1); DRAIN: a writer waits for its
+// stores (vmcnt(0)) before the barrier that ends a step.  k_terms_wg below is the body with the defaults of pdh_terms_tables.h (sc1|nt,
+// drained) and all the library instantiates; -DPDHT_VARIANTS builds add k_terms_wg_base, the policy before (nt, in flight), and
+// tools/paired_bench.py times the two in turn on one resident problem.  (The policy is an argument of the body, not of the kernels: a
+// kernel's symbol keeps its three arguments, by which tools/device_code_diff.py and tests/test_isa_lint.py find the instantiations.)
+template <int W, bool SHIFTED, int PMAX, int AUX, bool DRAIN>
+__device__ __forceinline__ void terms_wg(const PdhDev &P, const PdhTerms &T, const int n_owned)
 {
   constexpr int N1D = 4, BASIS = 0;
   using K = Kind<N1D, BASIS>;
@@ -272,7 +281,7 @@ __global__ void __launch_bounds__(PDH_WAVE *(W + WG_BUILDERS), 1) k_terms_wg(con
       const int first_int = nsfb > 0 ? 1 : 0; // the boundary run, if any, is run 0
       const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(P.values + rbase, 0, NF * rlen * 8, 0x00020000);
       auto row_store = [&](double v, uint32_t lane_bytes, uint32_t row_bytes) {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, WG_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, v), vrs, (int)lane_bytes, (int)row_bytes, AUX);
       };
       const uint32_t row0_bytes = (uint32_t)R0 * (uint32_t)rlen * 8u, rstep = (uint32_t)rlen * 8u;
       // coupling column `col` (0 .. 63) of the block of interior run `fl` (ascending block order without the own block), per lane
@@ -416,9 +425,24 @@ __global__ void __launch_bounds__(PDH_WAVE *(W + WG_BUILDERS), 1) k_terms_wg(con
               });
             }
         }
+      if constexpr (DRAIN)
+        __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0) alone (gfx9 encoding: expcnt 7 and lgkmcnt 15 wait for nothing)
       PDHW_MARK(s, sbase, 1);
       __syncthreads(); // tables of the next polytope in the other buffer; this one may be overwritten
       PDHW_MARK(s, sbase, 2);
     }
 }
+
+template <int W, bool SHIFTED, int PMAX>
+__global__ void __launch_bounds__(PDH_WAVE *(W + WG_BUILDERS), 1) k_terms_wg(const PdhDev P, const PdhTerms T, const int n_owned)
+{
+  terms_wg<W, SHIFTED, PMAX, WG_STORE_AUX, WG_DRAIN>(P, T, n_owned);
+}
+#ifdef PDHT_VARIANTS
+template <int W, bool SHIFTED, int PMAX>
+__global__ void __launch_bounds__(PDH_WAVE *(W + WG_BUILDERS), 1) k_terms_wg_base(const PdhDev P, const PdhTerms T, const int n_owned)
+{
+  terms_wg<W, SHIFTED, PMAX, WG_BASE_STORE_AUX, WG_BASE_DRAIN>(P, T, n_owned);
+}
+#endif
 } // namespace pdht

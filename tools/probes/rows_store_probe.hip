@@ -157,8 +157,14 @@ __global__ void __launch_bounds__(64 * SHARE) k_rows_shared(double *v, unsigned 
 // the first idle wave (needs 768 threads) - the writers never wait for the counter.
 // drain 0: a writer goes to the barrier with its stores in flight; 1: every writer waits for its stores first (vmcnt(0)); 2: wave 0
 // alone does (what the atomic of k_rows_shared costs its wave 0: vmcnt retires in order)
+// worder 0: piece-major writers (wave w: its 8 rows of piece 0, then of piece 1, ... - 8 stores of 512 bytes a row apart, what
+// k_terms_wg does); 1: row-major (wave w takes 4 consecutive rows at a time, two passes per polytope; for each row the pieces in
+// ascending order, so a pass writes one contiguous ascending 4 * nb * 512 bytes: 14 KB with 7 pieces).
+// tab != nullptr: the four idle waves also READ 3 KB per polytope (48 lanes x 16 bytes each) from a table of n_poly x 3 KB, at the
+// start of the step in which the writers fill that polytope - the kernel's read traffic (0.1 GB per launch) among the stores.
 template <int AUX>
-__global__ void __launch_bounds__(768, 1) k_rows_team(double *v, unsigned *sched, int n_poly, int nb, int spin, int S, int order, int drain)
+__global__ void __launch_bounds__(768, 1)
+  k_rows_team(double *v, unsigned *sched, int n_poly, int nb, int spin, int S, int order, int drain, int worder = 0, const double *tab = nullptr)
 {
   extern __shared__ double lds[];
   __shared__ int nxt[2];
@@ -179,18 +185,38 @@ __global__ void __launch_bounds__(768, 1) k_rows_team(double *v, unsigned *sched
             for (int k = 0; k < 64; ++k)
               acc = acc * 1.0000001 + 1e-9;
           const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(v + (size_t)slot * 64 * rlen, 0, 64 * rlen * 8, 0x00020000);
-          for (int b = 0; b < nb; ++b)
-            {
-              unsigned off = 64u * 8u * (unsigned)b + (unsigned)(w * 8) * (unsigned)rlen * 8u;
+          if (worder == 0)
+            for (int b = 0; b < nb; ++b)
+              {
+                unsigned off = 64u * 8u * (unsigned)b + (unsigned)(w * 8) * (unsigned)rlen * 8u;
 #pragma unroll
-              for (int r = 0; r < 8; ++r)
-                {
-                  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, acc + r), rs, lane * 8, off, AUX);
-                  off += (unsigned)rlen * 8u;
-                }
-            }
+                for (int r = 0; r < 8; ++r)
+                  {
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, acc + r), rs, lane * 8, off, AUX);
+                    off += (unsigned)rlen * 8u;
+                  }
+              }
+          else
+            for (int pass = 0; pass < 2; ++pass)
+              {
+                unsigned off = (unsigned)(w * 8 + pass * 4) * (unsigned)rlen * 8u; // (rows are contiguous: the pass ascends by 512)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                  for (int b = 0; b < nb; ++b)
+                    {
+                      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2_t, acc + r), rs, lane * 8, off, AUX);
+                      off += 512u;
+                    }
+              }
           if (drain == 1 || (drain == 2 && w == 0))
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+      else if (tab && lane < 48)
+        {
+          typedef double d2_t __attribute__((ext_vector_type(2)));
+          const d2_t t = reinterpret_cast<const d2_t *>(tab + (size_t)slot * 384)[(w - 8) * 48 + lane];
+          if (t.x + t.y == 12345.0) // (never: the table holds zeros; keeps the load)
+            lds[threadIdx.x] = t.x;
         }
       __syncthreads();
       slot = order == 2 ? nxt[k & 1] : slot + step;
@@ -368,6 +394,46 @@ int main()
                 threads / 64 - 8, per_cu, S, order == 2 ? "by counter " : (order ? "interleaved" : "consecutive"),
                 drain == 1 ? "writers drain their stores" : (drain ? "wave 0 drains its stores  " : "stores left in flight     "), grid, spin, ms, n * 8.0 / ms / 1e9);
   };
+  // ROWS_PROBE_ROW_MAJOR=1: only the writers' address order in the team geometry, polytopes by counter (profiles/r14_probe_row_major.txt):
+  // piece-major against row-major, nt and sc1|nt, stores in flight and drained, three alternating repeats; then nt with the idle waves
+  // reading the kernel's 3 KB per polytope
+  if (getenv("ROWS_PROBE_ROW_MAJOR"))
+    {
+      double *tab;
+      CHECK(hipMalloc(&tab, (size_t)NP * 384 * sizeof(double)));
+      CHECK(hipMemset(tab, 0, (size_t)NP * 384 * sizeof(double)));
+      auto run_order = [&](auto aux_, int worder, int drain, const double *t) {
+        constexpr int AUX = decltype(aux_)::value;
+        const size_t lds = 96 * 1024;
+        CHECK(hipFuncSetAttribute((const void *)k_rows_team<AUX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const int grid = 256;
+        auto launch = [&] { hipLaunchKernelGGL(k_rows_team<AUX>, dim3(grid), dim3(768), lds, 0, v, sched, NP, NB, 16, 128, 2, drain, worder, t); };
+        launch();
+        CHECK(hipDeviceSynchronize());
+        CHECK(hipEventRecord(e0));
+        for (int i = 0; i < 5; ++i)
+          launch();
+        CHECK(hipEventRecord(e1));
+        CHECK(hipDeviceSynchronize());
+        float ms;
+        CHECK(hipEventElapsedTime(&ms, e0, e1));
+        ms /= 5;
+        std::printf("aux %2d  team by counter, %s, %s, %s: %.3f ms  %.2f TB/s\n", AUX, worder ? "row-major  " : "piece-major",
+                    drain ? "writers drain their stores" : "stores left in flight     ", t ? "idle waves read 3 KB/polytope" : "no reads", ms, n * 8.0 / ms / 1e9);
+      };
+      for (int rep = 0; rep < 3; ++rep)
+        for (int drain : {0, 1})
+          for (int worder : {0, 1})
+            {
+              run_order(std::integral_constant<int, 2>{}, worder, drain, nullptr);
+              run_order(std::integral_constant<int, 18>{}, worder, drain, nullptr);
+            }
+      for (int rep = 0; rep < 3; ++rep)
+        for (int worder : {0, 1})
+          for (const double *t : {(const double *)nullptr, (const double *)tab})
+            run_order(std::integral_constant<int, 2>{}, worder, 0, t);
+      return 0;
+    }
   for (int rep = 0; rep < 3; ++rep)
     {
       run_shared(std::integral_constant<int, 4>{}, 16, 16);
