@@ -239,7 +239,20 @@ void *pdh_stream(pdh_ctx *ctx); /* hipStream_t the kernels are launched on */
  *                      The library stays transport-free (no RCCL/MPI dependency in the C ABI); bench.py drives it with
  *                      torch.distributed (RCCL).  Both ranks derive the block order of a peer buffer from the global dof
  *                      numbers of the cut faces, so no index lists are exchanged.  Results equal PDH_EXCHANGE_NONE up to
- *                      rounding (1e-14 relative).  Mode changes take effect at the next pdh_set_problem*.              */
+ *                      rounding (1e-14 relative).  Mode changes take effect at the next pdh_set_problem*.
+ *                      The wire format (n = dofs per polytope, blocks of n * n doubles): d_send holds one segment per peer
+ *                      in rank order, send_count[peer] doubles each (0 for the rank itself and for peers without a common
+ *                      face); d_recv likewise, recv_count[peer] doubles from every peer.  A segment carries
+ *                        1. the M21 blocks of the cut faces towards that peer, ascending by (first dof of the side-0
+ *                           polytope P, first dof of the side-1 polytope Q): plain [row of Q][column of P] - A[Q, P];
+ *                        2. one M22 block per distinct side-1 polytope Q of those faces, ascending by its first dof: the
+ *                           sum over the sender's cut faces into Q of their contribution to A[Q, Q], in the layout of
+ *                           Q's diagonal block - plain [row][column] with diag_first = 0; with diag_first = 1 row R holds
+ *                           column R first, then the columns 0 .. R-1, then R+1 .. n-1.
+ *                      A polytope cut off from several peers receives one M22 block from each; pdh_exchange_apply adds
+ *                      them to the diagonal block in peer order and STORES the M21 blocks (the assembly writes nothing
+ *                      there: between pdh_assemble_device and pdh_exchange_apply those entries hold what stood there
+ *                      before).                                                                                        */
 #define PDH_EXCHANGE_NONE 0
 #define PDH_EXCHANGE_GHOST 1
 int pdh_set_exchange_mode(pdh_ctx *ctx, int mode);

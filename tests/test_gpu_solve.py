@@ -13,6 +13,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import aniso_meshes as am
+from device_buffers import Device as _Device
 import golden_cases as gc
 from pcg_ref import diag_blocks, pcg, preconditioner
 
@@ -33,35 +34,6 @@ def _kernels(ctx, want=None):
     if want is not None:
         assert (used, kern) == want, (used, kern, want)
     return used, kern
-
-
-class _Device:
-    """Device buffers through the HIP runtime the library runs on."""
-
-    def __init__(self):
-        self.hip = C.CDLL("libamdhip64.so")
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.bufs = []
-
-    def put(self, a):
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), max(a.nbytes, 8)) == 0
-        self.bufs.append(p.value)
-        assert self.hip.hipMemcpy(p, C.c_void_p(a.ctypes.data), a.nbytes, 1) == 0
-        return p.value
-
-    def get(self, ptr, n):
-        out = np.empty(n)
-        assert self.hip.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(ptr), out.nbytes, 2) == 0
-        return out
-
-    def free(self):
-        for p in self.bufs:
-            self.hip.hipFree(C.c_void_p(p))
-        self.bufs = []
 
 
 def _handler(dim, cells, per, basis, p, kind="block", grid=None):

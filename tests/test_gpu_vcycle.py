@@ -11,6 +11,7 @@ import scipy.sparse.linalg as spla
 import pcg_ref
 import vcycle_cases as vc
 import vcycle_ref as vr
+from exchange_cases import block_pattern, coupled_polytopes, row_map
 from test_gpu_solve import _Device, _global_matrix
 
 pytestmark = pytest.mark.gpu
@@ -119,28 +120,15 @@ def _permuted_problem(ah, fe):
     c = flat.c
     n, n_agg = fe.n_dofs_per_cell, c.n_agg
     off = kw["dof_offset"].astype(np.int64)
-    rp, ci = kw["rowptr"].astype(np.int64), kw["colind"].astype(np.int64)
     new_off = n * np.random.default_rng(5).permutation(n_agg)
     assert np.any(new_off != off)
-    order = np.argsort(off)
-    owner = lambda cols: order[np.searchsorted(off[order], cols, side="right") - 1]  # polytope of a column
-    blocks = [np.unique(owner(ci[rp[off[P]]:rp[off[P] + 1]])) for P in range(n_agg)]  # the polytopes a row of P couples to
-    new_rp, new_ci = np.zeros(c.n_rows + 1, dtype=np.int64), []
-    for P in np.argsort(new_off):
-        cols = np.sort(np.concatenate([new_off[Q] + np.arange(n) for Q in blocks[P]]))
-        for i in range(n):
-            new_rp[new_off[P] + i + 1] = len(cols)
-            new_ci.append(cols)
-    new_rp = np.cumsum(new_rp)
-    kw.update(dof_offset=new_off.astype(np.int32), rowptr=new_rp, colind=np.concatenate(new_ci).astype(np.int32))
+    new_rp, new_ci = block_pattern(coupled_polytopes(off, kw["rowptr"], kw["colind"], n), new_off, n, False)
+    kw.update(dof_offset=new_off.astype(np.int32), rowptr=new_rp, colind=new_ci)
     kw.update(dim=c.dim, degree=c.degree, basis=c.basis, n_agg=c.n_agg, n_faces=c.n_faces, n_rows=c.n_rows, diag_first=0,
               reaction_c=c.reaction_c)
     prob = pa.Problem(**kw)
     prob.check()
-    old_to_new = np.zeros(c.n_rows, dtype=np.int64)
-    for P in range(n_agg):
-        old_to_new[off[P]:off[P] + n] = new_off[P] + np.arange(n)
-    return prob, old_to_new
+    return prob, row_map(off, new_off, n)
 
 
 def test_direct_solve_with_permuted_dof_offsets():
