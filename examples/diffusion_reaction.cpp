@@ -9,13 +9,19 @@
 //   solve :699-735, output_results :739-835   L2 and H1-seminorm errors against u = exp(x y z), summed over the ranks
 // Every "rank" describes ONLY its own polytopes and their ghost neighbours (pdh_problem::local = 1, Epetra column order: owned
 // columns first, ghosts behind) and assembles ONLY its rows (owner computes rows: no matrix traffic between ranks); the rows are
-// then put together for the host solver.  Usage: diffusion_reaction [n_refinements = 3] [n_ranks = 4] [n_local_agglomerates = 10]
+// then put together for the host solver.  With --device-solve the rows stay where they are and the ranks solve like the reference's
+// (:699-735), in lock-step through the C ABI (lockstep_solver.h: pdh_halo_setup, pdh_dcg_*; block Jacobi per rank): nothing but the
+// right-hand side and the solution crosses to the host.  Degree 4 keeps the host solver: its 125 dofs per polytope are beyond the 64 of
+// the device's block Jacobi, and point Jacobi does not bring CG to 1e-13 on these agglomerates in 20000 iterations.
+// Usage: diffusion_reaction [--device-solve] [n_refinements = 3] [n_ranks = 4] [n_local_agglomerates = 10]
 #include "../polydeal_amd/csrc/host/polydeal_host.h"
 #include "host_solver.h"
+#include "lockstep_solver.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 
 using namespace polydeal_hip;
@@ -23,9 +29,11 @@ using namespace polydeal_hip;
 int main(int argc, char **argv)
 {
   constexpr int dim = 3;
-  const int n_refinements = argc > 1 ? std::atoi(argv[1]) : 3;
-  const int n_ranks = argc > 2 ? std::atoi(argv[2]) : 4;
-  const int n_local_agglomerates = argc > 3 ? std::atoi(argv[3]) : 10;
+  const bool device_solve = argc > 1 && std::strcmp(argv[1], "--device-solve") == 0;
+  const int a0 = device_solve ? 1 : 0; // the positional arguments follow the flag
+  const int n_refinements = argc > a0 + 1 ? std::atoi(argv[a0 + 1]) : 3;
+  const int n_ranks = argc > a0 + 2 ? std::atoi(argv[a0 + 2]) : 4;
+  const int n_local_agglomerates = argc > a0 + 3 ? std::atoi(argv[a0 + 3]) : 10;
   const double reaction_coefficient = 0.5; // :853
   auto u_exact = [](const double *x) { return std::exp(x[0] * x[1] * x[2]); }; // Solution::value :258
   auto grad_exact = [](const double *x, double *g) {                            // Solution::gradient :264
@@ -51,6 +59,7 @@ int main(int argc, char **argv)
       ah.distribute_agglomerated_dofs(fe);
       const unsigned n = ah.n_dofs_per_cell(), N = ah.n_dofs(), nA = ah.n_agglomerates();
       const SipVariant variant = SipVariant::diffusion_reaction(fe); // penalty 10 p^2 (:366), id() < id() (:563), c = 0.5
+      const bool on_device = device_solve && n <= 64;
       // the global matrix the host solver works on (ascending columns: Trilinos rows are sorted by column)
       std::vector<int64_t> rowptr;
       std::vector<int32_t> colind;
@@ -96,14 +105,16 @@ int main(int argc, char **argv)
               const double x[3] = {F[r].fq_x[q], F[r].fq_x[nqf + q], F[r].fq_x[2 * nqf + q]};
               g_bdry[q] = u_exact(x);
             }
-          std::vector<double> local_values((size_t)(rowptr[r1] - rowptr[r0]));
-          if (pdh_assemble(ctx[r], local_values.data()) != PDH_OK ||
+          std::vector<double> local_values(on_device ? 0 : (size_t)(rowptr[r1] - rowptr[r0]));
+          if ((on_device ? pdh_assemble_device(ctx[r]) : pdh_assemble(ctx[r], local_values.data())) != PDH_OK ||
               pdh_assemble_rhs(ctx[r], f_vol.data(), g_bdry.data(), rhs.data() + r0) != PDH_OK)
             {
               std::fprintf(stderr, "rank %d: %s\n", r, pdh_last_error(ctx[r]));
               return 1;
             }
           t_assemble += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
+          if (on_device)
+            continue; // the rows stay in HBM
           // the rank's rows arrive in Epetra's local column order (owned columns first, ghost columns behind; colind of the local
           // description holds LOCAL column ids): translate them - local polytope a owns local columns col_offset[a] .. + n and global
           // columns dof_offset[a] .. + n - and put every row back into ascending global columns
@@ -131,8 +142,27 @@ int main(int argc, char **argv)
       std::cout << "Degree " << degree << ": " << nA << " agglomerates on " << n_ranks << " ranks, " << N << " dofs" << std::endl;
       std::cout << "Time taken by assemble_system() (all ranks, set-up included): " << t_assemble << " seconds" << std::endl;
       std::vector<double> solution;
-      const int its = example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
-      std::fprintf(stderr, "  (%d CG iterations)\n", its);
+      if (device_solve && !on_device)
+        std::cout << "device solve: not for " << n << " dofs per polytope (block Jacobi takes at most 64), host solver" << std::endl;
+      if (on_device)
+        {
+          for (int r = 0; r < n_ranks; ++r)
+            if (pdh_setup_preconditioner(ctx[r], PDH_PREC_BLOCK_JACOBI) != PDH_OK)
+              {
+                std::fprintf(stderr, "rank %d: %s\n", r, pdh_last_error(ctx[r]));
+                return 1;
+              }
+          solution.assign(N, 0.0);
+          const int its = example_solver::solve_cg_lockstep(ctx, splits, rhs, solution);
+          if (its < 0)
+            return 1;
+          std::cout << "device solve: " << its << " iterations on " << n_ranks << " ranks" << std::endl;
+        }
+      else
+        {
+          const int its = example_solver::solve_cg(rowptr, colind, values, (int)n, rhs, solution);
+          std::fprintf(stderr, "  (%d CG iterations)\n", its);
+        }
       // errors: every rank the squares over its own polytopes, summed like Utilities::MPI::sum (:736-745 of poly_utils.h)
       double l2sq = 0.0, h1sq = 0.0;
       for (int r = 0; r < n_ranks; ++r)

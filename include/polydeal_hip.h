@@ -667,6 +667,91 @@ int pdh_matrix_free_vmult_device(pdh_ctx *ctx, const double *d_x, double *d_y); 
 int pdh_set_smoother_operator(pdh_ctx *ctx, int op);
 int pdh_smoother_operator(pdh_ctx *ctx);
 
+/* Solving on N ranks: local vectors, their halo, y = A x on them and CG by reverse communication (pdh_dist.hip, pdh_capi_dist.cpp; the
+ * plan: pdh_halo_plan.cpp).  The counterpart of the reference's solve on its MPI ranks (examples/diffusion_reaction.cc:699-735).  Like the
+ * exchange above the library stays transport-free: it says WHAT has to move, the caller moves it (RCCL, MPI, a copy).
+ *   A rank owns the contiguous rows [row_begin, row_end) of its resident problem; row_splits [n_ranks + 1] are the first rows of all
+ * ranks, ascending, row_splits[r] .. row_splits[r + 1] the range of rank r.  Ownership of a ghost comes from row_splits alone (agg_rank
+ * is not read), so every description pdh_vmult serves is served: global with a row range, rank-local, col_offset, Cartesian, more than
+ * 64 dofs per polytope, both layouts.  PDH_EXCHANGE_NONE only (a problem set in PDH_EXCHANGE_GHOST mode: PDH_EUNSUPPORTED).
+ *   The LOCAL VECTOR of a rank has n_owned_rows + n_ghost_rows doubles: its owned rows in order, then one block of n doubles (n = dofs
+ * per polytope) for every distinct ghost polytope - one whose block appears in an owned row and whose rows another rank owns -
+ * ascending by first global dof.  Ranges are contiguous, so this ghost tail is grouped by owning rank in rank order: the tail IS the
+ * receive buffer, recv_count[peer] doubles from every peer one after the other, and a transport receives straight into
+ * d_v + n_owned_rows; nothing is unpacked.
+ *   The SEND BUFFER holds one segment per peer in rank order, send_count[peer] doubles (0 for the rank itself and for peers without a
+ * common face).  The segment for peer d holds the owned polytopes that have a coupled block in d's range, ascending by first global
+ * dof, n doubles each, in dof order; a polytope needed by several peers appears once per peer.
+ *   REQUIREMENT: the block pattern is structurally symmetric - if the rows of P hold a block of Q, the rows of Q hold a block of P (the
+ * DG face-neighbour pattern is).  Then the segment rank s sends to d is exactly the part of d's ghost tail that s owns, both derived by
+ * each side from its own description and row_splits: no index lists travel, as for pdh_exchange_layout.
+ *   pdh_check_halo    host-only, no GPU: the per-peer sizes in doubles and pdh_halo_info for a description and its row range.  The halo
+ *                     follows from the block pattern, so only the sizes, dof_offset and the face list are read and checked: a
+ *                     description without its point arrays (the view pdh_set_problem_cartesian takes) is served too.
+ *   pdh_halo_setup    the same for the resident problem, and builds the plan on the device (it is NOT built by pdh_set_problem*; a
+ *                     second call replaces it; it is freed with the problem).
+ * Both refuse with PDH_EINVAL: n_ranks < 1 or a NULL argument; row_splits that are not ascending; row_splits none of whose ranges is
+ * [row_begin, row_end); row_splits that cut a polytope (a split strictly inside the n dofs of an owned or ghost polytope); a ghost
+ * block outside [row_splits[0], row_splits[n_ranks]).
+ *   pdh_halo_pack_device   gathers the send buffer from the owned part of d_v: whole blocks, contiguous loads and stores, no atomics;
+ *                          d_send [sum send_count], asynchronous on the context's stream.  PDH_ESTATE before pdh_halo_setup.
+ *   pdh_vmult_local_device y = A v for owned rows, v a local vector, y [n_owned_rows]: the arithmetic of pdh_vmult_device - per row the
+ *                          same terms in the same order - with the columns found through a second block table of LOCAL positions, so
+ *                          the result equals pdh_vmult_device on the same context and the same numbers TO THE BIT.  `which` selects
+ *                          the polytopes whose rows are written (the others are not touched): all, the INTERIOR ones - every block
+ *                          owned, no ghost value read: the work a transport overlaps with the move - or the BOUNDARY ones.
+ *                          v and y must not overlap (PDH_EINVAL); PDH_ESTATE before pdh_halo_setup.                                  */
+typedef struct pdh_halo_info
+{
+  int64_t n_owned_rows, n_ghost_rows;
+  int32_t n_interior, n_boundary; /* owned polytopes */
+} pdh_halo_info;
+int pdh_check_halo(const pdh_problem *problem, int32_t row_begin, int32_t row_end, int n_ranks, const int32_t *row_splits,
+                   int64_t *send_count /* [n_ranks] doubles */, int64_t *recv_count, pdh_halo_info *info);
+int pdh_halo_setup(pdh_ctx *ctx, int n_ranks, const int32_t *row_splits, int64_t *send_count, int64_t *recv_count, pdh_halo_info *info);
+int pdh_halo_pack_device(pdh_ctx *ctx, const double *d_v /* local vector */, double *d_send);
+#define PDH_ROWS_ALL 0
+#define PDH_ROWS_INTERIOR 1 /* owned polytopes all of whose blocks are owned: need no ghost value */
+#define PDH_ROWS_BOUNDARY 2 /* the others                                                         */
+int pdh_vmult_local_device(pdh_ctx *ctx, const double *d_v, double *d_y /* [n_owned_rows] */, int which);
+
+/* Conjugate gradients over the ranks, by reverse communication: the recurrence, the stop rule and the fixed-order sums of pdh_solve_cg,
+ * with the halo moves and the global sums handed to the caller.  The library never calls a transport: pdh_dcg_begin and every
+ * pdh_dcg_resume return with a REQUEST in *next; the caller carries it out and calls pdh_dcg_resume, until the kind is PDH_DCG_DONE.
+ * Every rank makes the same calls in the same order.
+ *   HALO_BEGIN  start moving d_send (segments send_count of pdh_halo_setup) into the peers' ghost tails, this rank's being d_recv
+ *               (segments recv_count); the kernels that wrote d_send are queued on the context's stream.  May return before the data
+ *               has arrived: the library queues the INTERIOR product meanwhile.
+ *   HALO_END    make the context's stream see the completed receive (a synchronous transport did everything at HALO_BEGIN); the
+ *               library then queues the BOUNDARY product.
+ *   ALLREDUCE   sum the n_scalars doubles at d_scalars (device memory, written by kernels queued on the context's stream) over all
+ *               ranks, in place, with the SAME bits on every rank (e.g. added in rank order).
+ * One iteration is one halo (of p), one all-reduce of p^T A p and one of (r^T z, r^T r); the start moves the halo of x0 and reduces
+ * (r^T z, r^T r, b^T b).  Every rank reads the reduced ||r||^2 back, so all ranks stop in the same iteration - when ||r||_2 <=
+ * max(abs_tol, rel_tol ||b||_2) over ALL rows, tested before every iteration - and at max_iter every rank gets PDH_ENOCONV (with
+ * next->kind = PDH_DCG_DONE, result and x filled).  With ONE rank the sequence is the same with zero counts, and the iterates are those
+ * of pdh_solve_cg_device.  d_b and d_x [n_owned_rows] are device memory, disjoint, and stay the caller's until DONE: x0 in, solution out.
+ *   Preconditioners: the rank-local kinds PDH_PREC_NONE, PDH_PREC_JACOBI, PDH_PREC_BLOCK_JACOBI of pdh_setup_preconditioner (which works
+ * on any row range).  PDH_PREC_CHEBYSHEV (with or without the float32 smoother or the matrix-free smoother operator), PDH_PREC_DIRECT and
+ * PDH_PREC_MULTIGRID are PDH_EUNSUPPORTED naming the kind: each of their inner products would need a halo of its own.
+ *   PDH_ESTATE: pdh_dcg_resume without a run (no pdh_dcg_begin, or the run ended); pdh_dcg_begin while a run is open; the halo not set
+ * up; the values changed since the preconditioner was set up, or the values or the preconditioner changed during a run.  A run ends at
+ * PDH_DCG_DONE, at any error return, and with the problem.                                                                             */
+#define PDH_DCG_DONE 0
+#define PDH_DCG_HALO_BEGIN 1
+#define PDH_DCG_HALO_END 2
+#define PDH_DCG_ALLREDUCE 3
+typedef struct pdh_dcg_request
+{
+  int32_t kind;         /* PDH_DCG_*                                         */
+  const double *d_send; /* HALO_BEGIN: [sum send_count]                      */
+  double *d_recv;       /* HALO_BEGIN, HALO_END: the ghost tail [sum recv_count] */
+  double *d_scalars;    /* ALLREDUCE                                         */
+  int32_t n_scalars;    /* ALLREDUCE: 1 .. 3                                 */
+} pdh_dcg_request;
+int pdh_dcg_begin(pdh_ctx *ctx, const pdh_cg_control *control, const double *d_b, double *d_x, pdh_dcg_request *next);
+int pdh_dcg_resume(pdh_ctx *ctx, pdh_dcg_request *next, pdh_cg_result *result /* filled at PDH_DCG_DONE */);
+
 /* Version / build info: "polydeal_hip <version> gfx950". */
 const char *pdh_version(void);
 

@@ -24,6 +24,9 @@ PDH_SMOOTHER_F64, PDH_SMOOTHER_F32 = 0, 1
 _SMOOTHER = {"f64": PDH_SMOOTHER_F64, "f32": PDH_SMOOTHER_F32}
 PDH_SMOOTHER_OP_STORED, PDH_SMOOTHER_OP_MATRIX_FREE = 0, 1
 _SMOOTHER_OP = {"stored": PDH_SMOOTHER_OP_STORED, "matrix_free": PDH_SMOOTHER_OP_MATRIX_FREE}
+PDH_ROWS_ALL, PDH_ROWS_INTERIOR, PDH_ROWS_BOUNDARY = 0, 1, 2
+_WHICH = {"all": PDH_ROWS_ALL, "interior": PDH_ROWS_INTERIOR, "boundary": PDH_ROWS_BOUNDARY}
+PDH_DCG_DONE, PDH_DCG_HALO_BEGIN, PDH_DCG_HALO_END, PDH_DCG_ALLREDUCE = 0, 1, 2, 3
 CG_MAX_ITER = 20000  # solve_cg's default max_iter (the loop bound of examples/host_solver.h)
 
 
@@ -39,6 +42,14 @@ class pdh_cg_control(C.Structure):
 
 class pdh_cg_result(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("residual0", C.c_double), ("residual", C.c_double)]
+
+
+class pdh_halo_info(C.Structure):
+    _fields_ = [("n_owned_rows", C.c_int64), ("n_ghost_rows", C.c_int64), ("n_interior", C.c_int32), ("n_boundary", C.c_int32)]
+
+
+class pdh_dcg_request(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("d_send", C.c_void_p), ("d_recv", C.c_void_p), ("d_scalars", C.c_void_p), ("n_scalars", C.c_int32)]
 
 
 class pdh_chebyshev_control(C.Structure):
@@ -133,6 +144,7 @@ EXPORTS = [
     "pdh_set_smoother_precision", "pdh_smoother_precision", "pdh_smoother_vmult_device",
     "pdh_galerkin_plan", "pdh_galerkin_device",
     "pdh_setup_matrix_free", "pdh_matrix_free_vmult", "pdh_matrix_free_vmult_device", "pdh_set_smoother_operator", "pdh_smoother_operator",
+    "pdh_check_halo", "pdh_halo_setup", "pdh_halo_pack_device", "pdh_vmult_local_device", "pdh_dcg_begin", "pdh_dcg_resume",
 ]
 
 # (pdh_transfer_matrices_1d and pdh_ptransfer_matrix_1d are bound below like the others; tests/test_capi_cpu.py matches this list against the names of
@@ -244,6 +256,12 @@ def _bind(lib):
     lib.pdh_matrix_free_vmult_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
     lib.pdh_set_smoother_operator.argtypes = [pdh_ctx_p, C.c_int]
     lib.pdh_smoother_operator.argtypes = [pdh_ctx_p]
+    lib.pdh_check_halo.argtypes = [P(pdh_problem), C.c_int32, C.c_int32, C.c_int, C.c_void_p, P(C.c_int64), P(C.c_int64), P(pdh_halo_info)]
+    lib.pdh_halo_setup.argtypes = [pdh_ctx_p, C.c_int, C.c_void_p, P(C.c_int64), P(C.c_int64), P(pdh_halo_info)]
+    lib.pdh_halo_pack_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p]
+    lib.pdh_vmult_local_device.argtypes = [pdh_ctx_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pdh_dcg_begin.argtypes = [pdh_ctx_p, P(pdh_cg_control), C.c_void_p, C.c_void_p, P(pdh_dcg_request)]
+    lib.pdh_dcg_resume.argtypes = [pdh_ctx_p, P(pdh_dcg_request), P(pdh_cg_result)]
     return real
 
 
@@ -294,6 +312,26 @@ _DTYPES = {
     "fq_w": np.float64, "fq_w_out": np.float64, "face_sigma": np.float64, "rowptr": np.int64, "colind": np.int32,
     "col_offset": np.int32, "agg_rank": np.int32,
 }
+
+
+def _halo_result(n_ranks, s, r, info):
+    return ([int(x) for x in s[:n_ranks]], [int(x) for x in r[:n_ranks]],
+            {"n_owned_rows": int(info.n_owned_rows), "n_ghost_rows": int(info.n_ghost_rows), "n_interior": int(info.n_interior),
+             "n_boundary": int(info.n_boundary)})
+
+
+def check_halo(prob, row_begin, row_end, row_splits):
+    """pdh_check_halo (host only, no GPU): (send_count, recv_count, info) of the vector halo of the rows [row_begin, row_end) of a
+    description (a Problem or anything with a `.c` pdh_problem) among the ranks of row_splits [n_ranks + 1]; counts in doubles per peer,
+    info = {n_owned_rows, n_ghost_rows, n_interior, n_boundary}."""
+    lib = load_library()
+    sp = np.ascontiguousarray(row_splits, dtype=np.int32)
+    n_ranks = len(sp) - 1
+    s, r, info = (C.c_int64 * max(n_ranks, 1))(), (C.c_int64 * max(n_ranks, 1))(), pdh_halo_info()
+    rc = lib.pdh_check_halo(C.byref(prob.c), row_begin, row_end, n_ranks, sp.ctypes.data, s, r, C.byref(info))
+    if rc != PDH_OK:
+        raise PdhError(rc, lib.pdh_last_error(None).decode())
+    return _halo_result(n_ranks, s, r, info)
 
 
 class Problem:
@@ -549,6 +587,11 @@ class Multigrid:
                 self.close()
         except Exception:
             pass
+
+
+def _request(req):
+    return {"kind": int(req.kind), "d_send": req.d_send or 0, "d_recv": req.d_recv or 0, "d_scalars": req.d_scalars or 0,
+            "n_scalars": int(req.n_scalars)}
 
 
 class Context:
@@ -847,6 +890,46 @@ class Context:
         """Device pointers (ints); d_x holds the initial guess and receives the solution.  Returns info (PDH_ENOCONV raises
         PdhError carrying .info; d_x then holds the last iterate)."""
         return self._cg(self.lib.pdh_solve_cg_device, C.c_void_p(d_b), C.c_void_p(d_x), rel_tol, abs_tol, max_iter, lambda e: None)
+
+    # -- solving over several ranks (include/polydeal_hip.h: pdh_halo_*, pdh_vmult_local_device, pdh_dcg_*) ----------------
+    def halo_setup(self, row_splits):
+        """Builds the halo plan of the resident problem among the ranks of row_splits [n_ranks + 1]; returns (send_count, recv_count,
+        info) like check_halo.  The local vector has info['n_owned_rows'] + info['n_ghost_rows'] doubles."""
+        sp = np.ascontiguousarray(row_splits, dtype=np.int32)
+        n_ranks = len(sp) - 1
+        s, r, info = (C.c_int64 * max(n_ranks, 1))(), (C.c_int64 * max(n_ranks, 1))(), pdh_halo_info()
+        self._chk(self.lib.pdh_halo_setup(self.h, n_ranks, sp.ctypes.data, s, r, C.byref(info)))
+        return _halo_result(n_ranks, s, r, info)
+
+    def halo_pack(self, d_v, d_send):
+        """Gathers the send buffer from the owned part of the local vector; device pointers (ints), asynchronous."""
+        self._chk(self.lib.pdh_halo_pack_device(self.h, C.c_void_p(d_v), C.c_void_p(d_send or 0)))
+
+    def vmult_local(self, d_v, d_y, which="all"):
+        """y = A v on the local vector for the rows of 'all' | 'interior' | 'boundary' polytopes (or PDH_ROWS_*); device pointers
+        (ints), asynchronous on the context's stream."""
+        self._chk(self.lib.pdh_vmult_local_device(self.h, C.c_void_p(d_v), C.c_void_p(d_y), _WHICH[which] if isinstance(which, str) else int(which)))
+
+    def dcg_begin(self, d_b, d_x, rel_tol=1e-13, abs_tol=0.0, max_iter=None):
+        """Opens a CG run over the ranks (pdh_dcg_begin); d_b, d_x [n_owned_rows] device pointers (ints).  Returns the first request
+        as a dict {kind, d_send, d_recv, d_scalars, n_scalars} (kind: PDH_DCG_*)."""
+        ctl = pdh_cg_control(CG_MAX_ITER if max_iter is None else int(max_iter), float(rel_tol), float(abs_tol))
+        req = pdh_dcg_request()
+        self._chk(self.lib.pdh_dcg_begin(self.h, C.byref(ctl), C.c_void_p(d_b), C.c_void_p(d_x), C.byref(req)))
+        return _request(req)
+
+    def dcg_resume(self):
+        """Resumes the run after the caller carried out the last request: (request, info), info = {iterations, residual0, residual}
+        once request['kind'] is PDH_DCG_DONE, else None.  PDH_ENOCONV raises PdhError carrying .info (the run is over)."""
+        req, res = pdh_dcg_request(), pdh_cg_result()
+        rc = self.lib.pdh_dcg_resume(self.h, C.byref(req), C.byref(res))
+        info = {"iterations": int(res.iterations), "residual0": float(res.residual0), "residual": float(res.residual)}
+        if rc == PDH_ENOCONV:
+            e = PdhError(rc, self.lib.pdh_last_error(self.h).decode())
+            e.info = info
+            raise e
+        self._chk(rc)
+        return _request(req), (info if req.kind == PDH_DCG_DONE else None)
 
     def set_algorithm(self, alg):
         """'auto' | 'direct' (MFMA contraction over the points) | 'moment' (Legendre moments + sum factorisation)."""

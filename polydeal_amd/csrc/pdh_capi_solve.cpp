@@ -4,6 +4,7 @@
 // (kernels: pdh_dense.hip) is one more preconditioner; the V-cycle (pdh_capi_mg.cpp) composes the helpers of this unit.  The smoother may
 // read a float32 copy of the matrix and of the block inverses instead (pdh_set_smoother_precision; kernels: pdh_shadow.hip).
 #include "pdh_ctx.h"
+#include "pdh_cg_run.h"
 #include "pdh_dense.h"
 #include "pdh_launch.h"
 #include "pdh_shadow.h"
@@ -165,7 +166,7 @@ extern "C" int pdh_setup_preconditioner(pdh_ctx *ctx, int kind)
   return PDH_OK;
 }
 
-static int prec_checks(pdh_ctx *ctx)
+int pdh_prec_checks(pdh_ctx *ctx)
 {
   if (ctx->mg_gone)
     return fail(ctx, PDH_ESTATE, "the multigrid preconditioner of this context was destroyed: the context fell back to PDH_PREC_NONE, set a "
@@ -245,7 +246,7 @@ extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *
   // in place is served (a slot's r is read before its z is written); a shifted z would overwrite r of slots not read yet
   if (d_r != d_z && overlap(d_r, ctx->prob.n_rows_owned, d_z, ctx->prob.n_rows_owned))
     return fail(ctx, PDH_EINVAL, "r and z overlap partially (they must be the same array or disjoint)");
-  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(pdh_prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   const PdhSolveArgs A = pdh_solve_args(ctx);
   if (ctx->prec_kind == PDH_PREC_DIRECT || ctx->prec_kind == PDH_PREC_MULTIGRID)
@@ -266,70 +267,6 @@ extern "C" int pdh_precondition_device(pdh_ctx *ctx, const double *d_r, double *
   return pdh_prec_apply(ctx, ctx, A, d_r, d_z, nullptr, nullptr, ctx->stream);
 }
 
-// The preconditioned CG recurrence on the resident matrix, queued on the context's stream: the loop of examples/host_solver.h (q = A p,
-// alpha, x and r, z, beta, p) with every scalar kept on the device.  After each of start() / step() `n_scalars` doubles from
-// scal[first_scalar] are in ctx->pinned and the stream is idle - what they are and what follows from them is the caller's.
-// kind: the preconditioner of the fused update; chain: an application z = M r queued after it instead (kind none leaves z alone) -
-// the Chebyshev chain p(P^-1 A) P^-1, the dense inverse or the V-cycle attached to the context - whose last kernel writes the partials
-// of r^T z.
-struct CgRun
-{
-  pdh_ctx *ctx;
-  const PdhSolveArgs A;
-  const int kind;
-  const int chain; // PDH_PREC_NONE (no chain) | PDH_PREC_CHEBYSHEV | PDH_PREC_DIRECT | PDH_PREC_MULTIGRID
-  const int64_t N;
-  const int n_owned;
-  hipStream_t st;
-  double *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *part = nullptr, *scal = nullptr;
-  const double *dinv = nullptr;
-
-  CgRun(pdh_ctx *c, int kind_, int chain_)
-    : ctx(c), A(pdh_solve_args(c)), kind(kind_), chain(chain_), N(c->prob.n_rows_owned), n_owned(c->prob.n_owned), st(c->stream)
-  {
-    pdh_ctx::Problem::Solver &S = c->prob.sol;
-    r = S.r.get<double>(N), z = S.z.get<double>(N), p = S.p.get<double>(N), q = S.q.get<double>(N);
-    part = S.part.get<double>((size_t)PDH_CG_NPART * n_owned);
-    scal = S.scal.get<double>(PDH_CG_NSCALARS);
-    if (!c->pinned && hipHostMalloc((void **)&c->pinned, PDH_CG_NSCALARS * sizeof(double), hipHostMallocDefault) != hipSuccess)
-      c->pinned = nullptr;
-    dinv = S.dinv.ptr<double>();
-  }
-  bool ok() const { return r && z && p && q && part && scal && ctx->pinned; }
-  int apply_chain()
-  {
-    if (chain == PDH_PREC_MULTIGRID)
-      return pdh_mg_cycle(ctx->mg, r, z, true, r, part);
-    return chain == PDH_PREC_NONE ? PDH_OK : pdh_prec_apply(ctx, ctx, A, r, z, r, part, st);
-  }
-  int read_back(int first_scalar, int n_scalars)
-  {
-    PDH_HIP(ctx, hipMemcpyAsync(ctx->pinned, scal + first_scalar, n_scalars * sizeof(double), hipMemcpyDeviceToHost, st));
-    PDH_HIP(ctx, hipStreamSynchronize(st));
-    return PDH_OK;
-  }
-  // r = b - A x, z = P^-1 r, p = z
-  int start(const double *b, const double *x, int first_scalar, int n_scalars)
-  {
-    PDH_HIP(ctx, pdh_launch_vmult(&A, x, q, nullptr, st));
-    PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_INIT, kind, dinv, b, q, nullptr, nullptr, r, z, scal, part, st));
-    PDH_TRY(apply_chain());
-    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 0, scal, st));
-    PDH_HIP(ctx, pdh_launch_cg_direction(N, 1, z, p, scal, st));
-    return read_back(first_scalar, n_scalars);
-  }
-  int step(double *x, int first_scalar, int n_scalars)
-  {
-    PDH_HIP(ctx, pdh_launch_vmult(&A, p, q, part + (size_t)PDH_PART_PQ * n_owned, st));
-    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 1, scal, st));
-    PDH_HIP(ctx, pdh_launch_cg_update(&A, PDH_UPD_STEP, kind, dinv, nullptr, q, p, x, r, z, scal, part, st));
-    PDH_TRY(apply_chain());
-    PDH_HIP(ctx, pdh_launch_cg_finalise(part, n_owned, 2, scal, st));
-    PDH_HIP(ctx, pdh_launch_cg_direction(N, 0, z, p, scal, st));
-    return read_back(first_scalar, n_scalars);
-  }
-};
-
 extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const double *d_b, double *d_x, pdh_cg_result *res)
 {
   PDH_TRY(need_problem(ctx, "pdh_solve_cg"));
@@ -340,7 +277,7 @@ extern "C" int pdh_solve_cg_device(pdh_ctx *ctx, const pdh_cg_control *c, const 
   PDH_TRY(all_rows_checks(ctx, "pdh_solve_cg", "the solver runs on", "the solver", " (no distributed Krylov solver)"));
   if (overlap(d_b, ctx->prob.n_rows_total, d_x, ctx->prob.n_rows_total))
     return fail(ctx, PDH_EINVAL, "b and x overlap");
-  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(pdh_prec_checks(ctx));
   PDH_TRY(pdh_row_fits_lds(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   const bool chained = ctx->prec_kind == PDH_PREC_CHEBYSHEV || ctx->prec_kind == PDH_PREC_DIRECT || ctx->prec_kind == PDH_PREC_MULTIGRID;
@@ -491,7 +428,7 @@ extern "C" int pdh_chebyshev_step_device(pdh_ctx *ctx, const double *d_b, double
     return fail(ctx, PDH_EINVAL, "b and x overlap");
   if (ctx->prec_kind != PDH_PREC_CHEBYSHEV)
     return fail(ctx, PDH_ESTATE, "pdh_chebyshev_step_device: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
-  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(pdh_prec_checks(ctx));
   PDH_HIP(ctx, hipSetDevice(ctx->device));
   return cheb_apply(ctx, pdh_solve_args(ctx), d_b, d_x, zero_initial_guess != 0, nullptr, nullptr);
 }
@@ -555,7 +492,7 @@ extern "C" int pdh_set_smoother_precision(pdh_ctx *ctx, int precision)
                                  "every level before pdh_mg_create");
   if (ctx->prec_kind != PDH_PREC_CHEBYSHEV || ctx->mg_gone)
     return fail(ctx, PDH_ESTATE, "pdh_set_smoother_precision: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
-  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(pdh_prec_checks(ctx));
   pdh_ctx::Problem::Solver &S = ctx->prob.sol;
   if (precision == PDH_SMOOTHER_F64)
     {
@@ -613,7 +550,7 @@ extern "C" int pdh_set_smoother_operator(pdh_ctx *ctx, int op)
                                  "every level before pdh_mg_create");
   if (ctx->prec_kind != PDH_PREC_CHEBYSHEV || ctx->mg_gone)
     return fail(ctx, PDH_ESTATE, "pdh_set_smoother_operator: the preconditioner set up last is not PDH_PREC_CHEBYSHEV");
-  PDH_TRY(prec_checks(ctx));
+  PDH_TRY(pdh_prec_checks(ctx));
   if (op == PDH_SMOOTHER_OP_MATRIX_FREE)
     {
       if (!ctx->prob.d_mf_tables)

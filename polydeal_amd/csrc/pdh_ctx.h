@@ -1,4 +1,4 @@
-// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_matfree.cpp, pdh_capi_transfer.cpp,
+// pdh_ctx.h — internal to the device driver (pdh_capi.cpp, pdh_capi_vectors.cpp, pdh_capi_solve.cpp, pdh_capi_dist.cpp, pdh_capi_matfree.cpp, pdh_capi_transfer.cpp,
 // pdh_capi_mg.cpp), not
 // installed: the context
 // behind the opaque pdh_ctx of include/polydeal_hip.h, error reporting, the one device-buffer type, the alloc / upload helpers of
@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -201,6 +202,17 @@ struct pdh_ctx
       bool f32 = false;
       bool matrix_free = false; // pdh_set_smoother_operator: the same products apply the operator from d_mf_tables
     } sol;
+    // pdh_halo_setup (pdh_dist.h): the plan of the local vector's halo on the device - the block lists with local positions, the
+    // sources of the send buffer's blocks, the three slot lists one after the other (all, interior, boundary) - and the send buffer
+    // of pdh_dcg_*; dcg: the open run of pdh_dcg_begin (pdh_capi_dist.cpp).  All of it goes with the problem.
+    struct Halo
+    {
+      bool ready = false;
+      int n_ranks = 0, n_interior = 0, n_boundary = 0;
+      int64_t n_owned_rows = 0, n_ghost_rows = 0, n_send = 0, n_recv = 0;
+      DevBuf blk_loc, pack_src, slots, send, red;
+    } halo;
+    std::shared_ptr<struct PdhDcgRun> dcg;
   } prob;
 
   // AUTO takes the row kernel where it applies (degree 1 since 12 waves per CU are resident: 0.21 vs 0.24-0.30 ms)
@@ -366,6 +378,8 @@ struct Staging
 PdhSolveArgs pdh_solve_args(const pdh_ctx *ctx);
 // the guard of the products: a problem resident (`name` in the message), x [n_rows_total] and y [owned rows] given and disjoint
 int pdh_vmult_vectors_check(pdh_ctx *ctx, const char *name, const void *x, const void *y);
+// PDH_ESTATE on `ctx` unless the preconditioner set up last is current for the values as they stand (what pdh_solve_cg* asks first)
+int pdh_prec_checks(pdh_ctx *ctx);
 int pdh_row_fits_lds(pdh_ctx *ctx); // PDH_EUNSUPPORTED on `ctx`: a row of more than 8192 entries (k_vmult keeps a column set in LDS)
 // One application of the Chebyshev polynomial of `ctx` to b: x <- x + p(P^-1 A) P^-1 (b - A x) (zero: x <- p(..) P^-1 b, x not read).
 // rcg / part: see pdh_launch_cheb_update.  Errors are reported on `report`.

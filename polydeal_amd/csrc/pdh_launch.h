@@ -159,6 +159,18 @@ hipError_t pdh_launch_cheb_update(const PdhSolveArgs *A, int first, int kind, co
 hipError_t pdh_launch_cg_direction(int64_t n_rows, int init, const double *z, double *p, const double *scal, hipStream_t stream);
 // one workgroup: partials -> scalars.  stage 0: rz, rr, bb;  1: pq, alpha;  2: rz, rr, beta
 hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, int stage, double *scal, hipStream_t stream);
+// its two halves, for sums that are added over several ranks in between: partials -> sums [3] of this rank (the stage's, the rest 0);
+// the reduced sums -> scalars
+hipError_t pdh_launch_cg_local_sum(const double *part, int n_owned, int stage, double *sums, hipStream_t stream);
+hipError_t pdh_launch_cg_finish(int stage, const double *sums, double *scal, hipStream_t stream);
+
+// pdh_dist.hip
+// send [n_blocks][n] = the blocks of n doubles at v + src[b]: whole blocks, contiguous within a block
+hipError_t pdh_launch_halo_pack(int n, int64_t n_blocks, const int64_t *src, const double *v, double *send, hipStream_t stream);
+// y = A v for the rows of the slots listed (k_vmult's arithmetic).  A->blk_dof holds LOCAL positions: v is a rank's local vector.
+// part (may be NULL): per slot LISTED, sum_i y_i v_i over the slot's own rows, at part[slot]
+hipError_t pdh_launch_vmult_local(const PdhSolveArgs *A, const int32_t *slots, int n_slots, const double *v, double *y, double *part,
+                                  hipStream_t stream);
 
 // pdh_dense.hip (pdh_dense.h: ld = pdh_dense_ld(n_rows), 1 <= n_rows <= PDH_DENSE_MAX_ROWS, else hipErrorInvalidValue)
 // D [ld][ld] (zeroed by the caller) = the resident rows, dense

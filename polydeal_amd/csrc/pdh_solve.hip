@@ -6,70 +6,18 @@
 // are added by ONE workgroup in slot order (k_cg_finalise).  No atomics: the same call on the same data gives the same bits.
 #include "pdh_solve.h"
 #include "pdh_launch.h"
+#include "pdh_vmult_row.h"
 
 #include <hip/hip_runtime.h>
 
 namespace
 {
-constexpr int W = 64;
+using pdh_row::row_dot;
+using pdh_row::W;
+using pdh_row::wave_sum;
 constexpr int PREC_NONE = 0, PREC_JACOBI = 1, PREC_BLOCK = 2; // PDH_PREC_* of include/polydeal_hip.h
 
-// sum over the 64 lanes; every lane gets the same bits (a + b = b + a at every butterfly stage)
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-  for (int m = W / 2; m > 0; m >>= 1)
-    v += __shfl_xor(v, m, W);
-  return v;
-}
-
-// Lane's share of one row: the terms k = k0 + 64 u + lane, u < NP.  The NP loads are issued before any of them is used (the last
-// piece of a row is clamped to its last entry and its surplus lanes discarded), so a wave has NP 512-byte pieces in flight.
-// Value position k holds ascending position a(k): k itself, or in the deal.II layout the diagonal first (k = 0 -> di = diag_L + i)
-// and the entries before it shifted by one (1 <= k <= di -> k - 1).
-template <int NP, bool DF>
-__device__ __forceinline__ double row_part(const double *__restrict__ vr, const double *xs, int k0, int rl, int di, int lane)
-{
-  double val[NP];
-#pragma unroll
-  for (int u = 0; u < NP; ++u)
-    {
-      const int k = k0 + u * W + lane;
-      val[u] = __builtin_nontemporal_load(vr + (k < rl ? k : rl - 1));
-    }
-  double sum = 0.0;
-#pragma unroll
-  for (int u = 0; u < NP; ++u)
-    {
-      const int k = k0 + u * W + lane;
-      const int a = DF ? (k == 0 ? di : (k <= di ? k - 1 : k)) : k;
-      sum += k < rl ? val[u] * xs[a < rl ? a : 0] : 0.0;
-    }
-  return sum;
-}
-
-template <bool DF>
-__device__ __forceinline__ double row_dot(const double *__restrict__ vr, const double *xs, int rl, int di, int lane)
-{
-  switch ((rl + W - 1) / W)
-    {
-    case 1: return row_part<1, DF>(vr, xs, 0, rl, di, lane);
-    case 2: return row_part<2, DF>(vr, xs, 0, rl, di, lane);
-    case 3: return row_part<3, DF>(vr, xs, 0, rl, di, lane);
-    case 4: return row_part<4, DF>(vr, xs, 0, rl, di, lane);
-    case 5: return row_part<5, DF>(vr, xs, 0, rl, di, lane);
-    case 6: return row_part<6, DF>(vr, xs, 0, rl, di, lane);
-    case 7: return row_part<7, DF>(vr, xs, 0, rl, di, lane);
-    case 8: return row_part<8, DF>(vr, xs, 0, rl, di, lane);
-    default:
-      {
-        double sum = 0.0;
-        for (int k0 = 0; k0 < rl; k0 += 8 * W)
-          sum += row_part<8, DF>(vr, xs, k0, rl, di, lane);
-        return sum;
-      }
-    }
-}
+// (wave_sum, row_part and row_dot - the arithmetic of a row - live in pdh_vmult_row.h, shared with pdh_dist.hip)
 
 // One wave per owned polytope.  The x of its column set (its blocks in value order) is gathered into LDS once and serves all n
 // rows.  Rows go two at a time (both rows' loads in flight before either is summed); the sum of row i lands in lane i % 64, whose
@@ -352,10 +300,12 @@ __global__ void __launch_bounds__(256) k_cg_direction(int64_t N, int init, const
     p[i] = init ? z[i] : z[i] + beta * p[i];
 }
 
-// One workgroup: thread t adds the partials t, t + 256, ... in order, then a fixed tree over the 256 threads.
-__global__ void __launch_bounds__(256) k_cg_finalise(const double *__restrict__ part, int n_owned, int stage, double *__restrict__ scal)
+// The two halves of turning partials into scalars.  cg_local_sum - one workgroup: thread t adds the partials t, t + 256, ... in order,
+// then a fixed tree over the 256 threads; the (up to three) sums of the stage are left in red[c][0].  cg_finish - one thread: the
+// scalars of the stage from its sums.  One rank runs both in one kernel (k_cg_finalise); over several ranks the sums of all ranks are
+// added between the two (k_cg_local_sum, the caller's all-reduce, k_cg_finish: pdh_dcg_*).
+__device__ __forceinline__ void cg_local_sum(const double *__restrict__ part, int n_owned, int stage, double (*red)[256])
 {
-  __shared__ double red[3][256];
   const int t = threadIdx.x;
   const int rows[3][3] = {{PDH_PART_RZ, PDH_PART_RR, PDH_PART_BB}, {PDH_PART_PQ, -1, -1}, {PDH_PART_RZ, PDH_PART_RR, -1}};
   for (int c = 0; c < 3; ++c)
@@ -375,28 +325,51 @@ __global__ void __launch_bounds__(256) k_cg_finalise(const double *__restrict__ 
           red[c][t] += red[c][t + h];
       __syncthreads();
     }
-  if (t == 0)
+}
+
+__device__ __forceinline__ void cg_finish(int stage, double s0, double s1, double s2, double *__restrict__ scal)
+{
+  if (stage == 0)
     {
-      const double s0 = red[0][0], s1 = red[1][0], s2 = red[2][0];
-      if (stage == 0)
-        {
-          scal[PDH_CG_RZ] = s0;
-          scal[PDH_CG_RR] = s1;
-          scal[PDH_CG_BB] = s2;
-        }
-      else if (stage == 1)
-        {
-          scal[PDH_CG_PQ] = s0;
-          scal[PDH_CG_ALPHA] = s0 != 0.0 ? scal[PDH_CG_RZ] / s0 : 0.0;
-        }
-      else
-        {
-          const double rz0 = scal[PDH_CG_RZ];
-          scal[PDH_CG_BETA] = rz0 != 0.0 ? s0 / rz0 : 0.0;
-          scal[PDH_CG_RZ] = s0;
-          scal[PDH_CG_RR] = s1;
-        }
+      scal[PDH_CG_RZ] = s0;
+      scal[PDH_CG_RR] = s1;
+      scal[PDH_CG_BB] = s2;
     }
+  else if (stage == 1)
+    {
+      scal[PDH_CG_PQ] = s0;
+      scal[PDH_CG_ALPHA] = s0 != 0.0 ? scal[PDH_CG_RZ] / s0 : 0.0;
+    }
+  else
+    {
+      const double rz0 = scal[PDH_CG_RZ];
+      scal[PDH_CG_BETA] = rz0 != 0.0 ? s0 / rz0 : 0.0;
+      scal[PDH_CG_RZ] = s0;
+      scal[PDH_CG_RR] = s1;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_cg_finalise(const double *__restrict__ part, int n_owned, int stage, double *__restrict__ scal)
+{
+  __shared__ double red[3][256];
+  cg_local_sum(part, n_owned, stage, red);
+  if (threadIdx.x == 0)
+    cg_finish(stage, red[0][0], red[1][0], red[2][0], scal);
+}
+
+// sums [3]: the stage's local sums (unused ones 0)
+__global__ void __launch_bounds__(256) k_cg_local_sum(const double *__restrict__ part, int n_owned, int stage, double *__restrict__ sums)
+{
+  __shared__ double red[3][256];
+  cg_local_sum(part, n_owned, stage, red);
+  if (threadIdx.x < 3)
+    sums[threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ void __launch_bounds__(64) k_cg_finish(int stage, const double *__restrict__ sums, double *__restrict__ scal)
+{
+  if (threadIdx.x == 0)
+    cg_finish(stage, sums[0], sums[1], sums[2], scal);
 }
 } // namespace
 
@@ -480,6 +453,22 @@ extern "C" hipError_t pdh_launch_cg_finalise(const double *part, int n_owned, in
   if (stage < 0 || stage > 2)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_cg_finalise, dim3(1), dim3(256), 0, stream, part, n_owned, stage, scal);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pdh_launch_cg_local_sum(const double *part, int n_owned, int stage, double *sums, hipStream_t stream)
+{
+  if (stage < 0 || stage > 2)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cg_local_sum, dim3(1), dim3(256), 0, stream, part, n_owned, stage, sums);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pdh_launch_cg_finish(int stage, const double *sums, double *scal, hipStream_t stream)
+{
+  if (stage < 0 || stage > 2)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(64), 0, stream, stage, sums, scal);
   return hipGetLastError();
 }
 

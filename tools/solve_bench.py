@@ -58,6 +58,12 @@ h-hierarchy of FE_DGQ(3) and with "FE_DGQ(1) on polytopes of 32^3 .. 2^3 cells, 
 iterations, ms per cycle, seconds, bytes of the level matrices; (c) FE_DGQ(3) on grown agglomerates of about 2^3 cells, which have no
 nested hierarchy: block-Jacobi CG against the p-V-cycle over the degrees 1 -> 2 -> 3 with a Chebyshev coarsest level.  (b) and (c) are
 reports: no condition is checked.
+Distributed section (--distributed W, alone; pdh_halo_setup, pdh_dcg_*), written to profiles/r15_distributed_cg.json unless --out says
+otherwise: the headline problem split by partition.balanced_row_splits into W rank-local contexts on ONE device, solved in lock-step
+(polydeal_amd/distributed.py).  Per iteration the halo pack, the interior and the boundary product, the fused update and the whole step,
+as wall times between stream synchronisations summed over the ranks (one device runs them one after the other); with W = 1 next to
+pdh_solve_cg_device on the same problem in the same process.  A report: no time is a condition.  One device playing W ranks shows neither
+the overlap of the interior product with the halo move nor an interconnect - there is no multi-GPU node to measure them on.
 Prints one JSON document (and writes it to --out)."""
 import argparse
 import json
@@ -875,6 +881,150 @@ def p_vcycle_case(pa, torch, cells, reps):
     return out
 
 
+def distributed_case(pa, torch, cells, W, reps):
+    """CG over W rank-local contexts of the headline problem on one device (see the module docstring)"""
+    import ctypes as C
+
+    from polydeal_amd import _capi
+    from polydeal_amd.distributed import _copy, _hip, _offsets, solve_cg_lockstep_device
+    from polydeal_amd.partition import balanced_row_splits
+
+    ah, fe = handler(pa, cells, "dgq")
+    var = pa.SipVariant.poisson_example(fe)
+    n, N = fe.n_dofs_per_cell, ah.n_dofs
+    splits = [int(v) for v in balanced_row_splits(ah.blocks_per_row(), n, W)]
+    ctxs, lay = [], []
+    t0 = time.time()
+    for r in range(W):
+        c = pa.Context(0)
+        ctxs.append(c)
+        c.set_problem(ah.flatten_local(var, splits[r], splits[r + 1], True, False, row_splits=splits), splits[r], splits[r + 1])
+        c.assemble_device()
+        c.setup_preconditioner("block_jacobi")
+        lay.append(c.halo_setup(splits))
+        c.synchronize()
+    setup_s = time.time() - t0
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    b = [torch.rand(splits[r + 1] - splits[r], dtype=torch.float64, device="cuda", generator=gen) for r in range(W)]
+    x = [torch.zeros_like(v) for v in b]
+    d_b, d_x = [v.data_ptr() for v in b], [v.data_ptr() for v in x]
+
+    def capped(cap):
+        for v in x:
+            v.zero_()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        try:
+            solve_cg_lockstep_device(ctxs, splits, d_b, d_x, rel_tol=0.0, max_iter=cap, layouts=lay)
+        except pa.PdhError as e:
+            if e.code != pa.PDH_ENOCONV:
+                raise
+        return time.perf_counter() - t
+    k, m = 2, 20
+    capped(k)
+    step_ms = median([(capped(k + m) - capped(k)) / m * 1e3 for _ in range(max(3, reps // 3))])
+
+    # the phases of an iteration: the lock-step loop again with a synchronisation after every piece
+    hip = _hip()
+    send_at, recv_at = [_offsets(l[0]) for l in lay], [_offsets(l[1]) for l in lay]
+    phases = {"halo_copy": [], "interior": [], "boundary": [], "allreduce_host": [], "update": [], "direction_readback_and_pack": []}
+
+    def timed(key, fn):
+        t = time.perf_counter()
+        fn()
+        for c in ctxs:
+            c.synchronize()
+        phases[key].append((time.perf_counter() - t) * 1e3)
+
+    def resume_all(reqs):
+        done = False
+        for r, c in enumerate(ctxs):
+            try:
+                reqs[r] = c.dcg_resume()[0]
+            except pa.PdhError as e:
+                if e.code != pa.PDH_ENOCONV:
+                    raise
+                done = True
+        return done
+    for v in x:
+        v.zero_()
+    torch.cuda.synchronize()
+    reqs = [c.dcg_begin(d_b[r], d_x[r], 0.0, 0.0, k + m) for r, c in enumerate(ctxs)]
+    stage, done = 0, False
+    while not done:
+        kind = reqs[0]["kind"]
+        if kind == _capi.PDH_DCG_HALO_BEGIN:
+            # (the pack was queued by the call that asked for the move and is timed with it; on its own: `standalone` below)
+            def move():
+                for s_ in range(W):
+                    for d_ in range(W):
+                        _copy(hip, reqs[d_]["d_recv"] + 8 * int(recv_at[d_][s_]), reqs[s_]["d_send"] + 8 * int(send_at[s_][d_]), lay[s_][0][d_], 3)
+            timed("halo_copy", move)
+            timed("interior", lambda: resume_all(reqs))
+        elif kind == _capi.PDH_DCG_HALO_END:
+            timed("boundary", lambda: resume_all(reqs))
+        elif kind == _capi.PDH_DCG_ALLREDUCE:
+            m_ = reqs[0]["n_scalars"]
+
+            def reduce_():
+                import numpy as np
+                parts = np.empty((W, m_))
+                for r in range(W):
+                    _copy(hip, parts[r].ctypes.data, reqs[r]["d_scalars"], m_, 2)
+                total = parts[0].copy()
+                for r in range(1, W):
+                    total += parts[r]
+                for r in range(W):
+                    _copy(hip, reqs[r]["d_scalars"], total.ctypes.data, m_, 1)
+            timed("allreduce_host", reduce_)
+            flag = []
+            timed("update" if m_ == 1 else "direction_readback_and_pack", lambda: flag.append(resume_all(reqs)))
+            done = flag[0]
+        else:
+            break
+    # (the first halo / products / reduction belong to the start)
+    # the three kernels of this unit on their own, all ranks one after the other
+    v = [torch.rand(l[2]["n_owned_rows"] + l[2]["n_ghost_rows"], dtype=torch.float64, device="cuda", generator=gen) for l in lay]
+    snd = [torch.empty(max(sum(l[0]), 1), dtype=torch.float64, device="cuda") for l in lay]
+    standalone = {}
+    for key, fn in (("pack", lambda r: ctxs[r].halo_pack(v[r].data_ptr(), snd[r].data_ptr())),
+                    ("interior", lambda r: ctxs[r].vmult_local(v[r].data_ptr(), x[r].data_ptr(), "interior")),
+                    ("boundary", lambda r: ctxs[r].vmult_local(v[r].data_ptr(), x[r].data_ptr(), "boundary")),
+                    ("all", lambda r: ctxs[r].vmult_local(v[r].data_ptr(), x[r].data_ptr(), "all"))):
+        ts = []
+        torch.cuda.synchronize()
+        for _ in range(reps + 1):
+            t = time.perf_counter()
+            for r in range(W):
+                fn(r)
+            for c in ctxs:
+                c.synchronize()
+            ts.append((time.perf_counter() - t) * 1e3)
+        standalone[key] = median(ts[1:])
+    per_iter = {key: median(v[1:]) if len(v) > 1 else None for key, v in phases.items()}
+    out = {"what": "FE_DGQ(3), %d^3 cells, polytopes of 2^3 cells: block-Jacobi CG over %d rank-local contexts on one device, lock-step" % (cells, W),
+           "caveat": "one device plays all ranks one after the other: no overlap of the interior product with the halo move and no "
+                     "interconnect (xGMI) is measured, there is no multi-GPU node; the times are wall times between stream synchronisations, "
+                     "summed over the ranks, launch and host latencies included.  A report, no time is a pass condition.",
+           "world": W, "n_dofs": N, "row_splits": splits, "setup_s_all_ranks": setup_s,
+           "halo": [{"send_doubles": int(sum(l[0])), "recv_doubles": int(sum(l[1])), "interior_polytopes": l[2]["n_interior"],
+                     "boundary_polytopes": l[2]["n_boundary"]} for l in lay],
+           "whole_step_ms_median": step_ms, "phase_ms_median": per_iter, "standalone_kernel_ms_median": standalone}
+    if W == 1:
+        cg_ms = cg_iteration_ms(pa, ctxs[0], torch, b[0], x[0], k, m, max(3, reps // 3))
+        out["pdh_solve_cg_device_iteration_ms_median_same_problem"] = cg_ms
+        out["whole_step_over_pdh_solve_cg_device"] = step_ms / cg_ms
+        out["parent_commit_cg_iteration_ms"] = {"source": "profiles/r06_solve_bench.json, FE_DGQ(3) diag_first (the tool's default mode)", "value": None}
+        try:
+            with open(os.path.join(ROOT, "profiles", "r06_solve_bench.json")) as f:
+                out["parent_commit_cg_iteration_ms"]["value"] = json.load(f)["cases"][0]["cg_iteration_ms_median"]
+        except (OSError, KeyError, IndexError, ValueError):
+            pass
+    for c in ctxs:
+        c.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cells", type=int, default=64, help="cells per axis (power of two); 64 = the headline problem")
@@ -893,11 +1043,30 @@ def main():
     ap.add_argument("--p-vcycle", action="store_true",
                     help="the p-multigrid section alone: p-transfer pairs, the headline solve over a p-then-h hierarchy, dgq3_grown "
                          "(default --out: profiles/r13_p_multigrid.json)")
+    ap.add_argument("--distributed", type=int, default=0, metavar="W",
+                    help="the distributed-CG section alone: the headline problem over W rank-local contexts on one device; several "
+                         "runs append to the same file (default --out: profiles/r15_distributed_cg.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
 
     import polydeal_amd as pa
+    if args.distributed:
+        path = args.out or os.path.join(ROOT, "profiles", "r15_distributed_cg.json")
+        out = {"tool": "tools/solve_bench.py --distributed W", "version": pa.load_library().pdh_version().decode(),
+               "device": torch.cuda.get_device_name(0), "runs": []}
+        if os.path.exists(path):  # runs of other W under the same build are kept
+            with open(path) as f:
+                old = json.load(f)
+            if old.get("version") == out["version"]:
+                out["runs"] = [r for r in old.get("runs", []) if r.get("world") != args.distributed]
+        out["runs"].append(distributed_case(pa, torch, args.cells, args.distributed, args.reps))
+        out["runs"].sort(key=lambda r: r["world"])
+        doc = json.dumps(out, indent=1)
+        with open(path, "w") as f:
+            f.write(doc + "\n")
+        print(doc)
+        return
     if args.p_vcycle:
         out = {"tool": "tools/solve_bench.py --p-vcycle", "version": pa.load_library().pdh_version().decode(),
                "device": torch.cuda.get_device_name(0)}
